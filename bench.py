@@ -11,8 +11,14 @@ SoA planes instead) pre-generated into an HBM ring of 64 ticks (not timed).  Eve
 for N > 1, all-gathers it over RCCL (the cfg 4 collective).  Weak scaling: per-GPU
 work is fixed as N grows.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, ms_per_step, ...).  --dump-outputs DIR also writes what the last timed step left (the
+state and the newest ensemble result) as DIR/<name>.npy.  --full adds every other figure and
+check: the tick kernel's own time and roofline, K = 1, the fused replay, cfg 3 / cfg 4 / cfg 5
+and the path rows, the sampled parity against the oracle and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -616,6 +622,41 @@ def cfg4_shard(dev, stream, ticks: int, trig):
     return res
 
 
+DUMP_SAMPLE = 1 << 18  # robots of a larger fleet that --dump-outputs keeps (27 floats each: 27 MiB)
+DUMP_SEED = 20240
+
+
+def dump_indices(n: int):
+    """The robots --dump-outputs writes: all of them up to DUMP_SAMPLE, else a fixed seeded
+    sample of DUMP_SAMPLE (sorted; the first and the last robot always among them)."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    idx = np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)
+    idx[:2] = (0, n - 1)
+    return np.unique(idx)
+
+
+def dump_outputs(path: str, x, P, ens) -> dict:
+    """Write what the timed path's caller holds after its last step as `path`/<name>.npy: the
+    state mean `x` [6][k] and packed covariance `P` [21][k] (float32) of the robots
+    `robot_index` [k] (float64) picks from this rank's fleet, and the newest collected ensemble
+    result (`ensemble_mean` [6], `ensemble_cov` [21], `ensemble_count` [1]; float64).  Returns
+    {name: shape} of the files written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    idx = dump_indices(x.shape[1])
+    arrays = {"robot_index": idx.astype(np.float64),
+              "x": np.ascontiguousarray(x[:, idx], dtype=np.float32),
+              "P": np.ascontiguousarray(P[:, idx], dtype=np.float32)}
+    if ens is not None:
+        arrays.update(ensemble_mean=np.asarray(ens[0], np.float64), ensemble_cov=np.asarray(ens[1], np.float64),
+                      ensemble_count=np.array([ens[2]], np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     cmd = launcher_cmd(sys.argv[1:], os.environ)
     if cmd is not None:  # --gpus N > 1 with no launcher: run the N ranks as a child
@@ -668,7 +709,19 @@ def main():
                          "(at world > 1 it always runs, reported as cfg4_16M)")
     ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg4_16M block")
     ap.add_argument("--cfg4-steps", type=int, default=64)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write the state the last timed step left (x, P; a fixed "
+                         "seeded sample of a fleet above 2^18 robots) and the newest ensemble result as "
+                         "DIR/<name>.npy (rank 0's; the same arguments give the same inputs every run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the tick kernel's own time and roofline, K = 1, the fused "
+                         "replay, the secondary configs and path rows, cfg4_16M, the ensemble check, the "
+                         "sampled parity and the CPU baseline (each as its own option selects); a run "
+                         "without --full times the steps and prints the headline fields only")
     args = ap.parse_args()
+    for opt in ("check_ensemble", "cfg4_16m"):
+        if getattr(args, opt) and not args.full:
+            ap.error(f"--{opt.replace('_', '-')} is part of the --full run: add --full")
 
     import numpy as np
     import torch
@@ -964,6 +1017,97 @@ def main():
     # the pending ensemble results, the final synchronise
     host_split = {"submit_ms": (t_sub - t0) * 1e3, "join_ms": (t_join - t_sub) * 1e3,
                   "sync_ms": (t1 - t_join) * 1e3}
+
+    def newest_ensemble():
+        """(mean, cov packed, robots counted, records folded or None) of the newest collected
+        ensemble result (None before the first): the native path's own fold, else the last
+        gathered records folded in rank order"""
+        if args.gather == "native" and native_stats[0] is not None:
+            return native_stats[0]
+        if not ev_count[0]:
+            return None
+        last = gathered[(ev_count[0] - 1) % n_events].cpu().numpy()
+        mean, cov = fmskf.ensemble_combine(6, last)
+        return mean, cov, float(last[:, 0].sum()), None
+
+    # --dump-outputs: the state and the ensemble result as the last timed step left them, read
+    # out before anything else runs on the engine
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, *eng.get_state(), newest_ensemble())
+
+    def ensemble_summary():
+        ne = newest_ensemble()
+        if ne is None:
+            return None
+        s = {"count": ne[2], "mean_theta": float(ne[0][2]), "var_vx": float(ne[1][9])}
+        if ne[3] is not None:
+            s["records_folded"] = ne[3]
+        return s
+
+    def headline(elapsed):
+        """the result line's fields a plain run reports; --full adds the rest after them"""
+        return {
+            "metric": METRIC,
+            "value": n_global * args.steps / elapsed,
+            "unit": "steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed * 1e3 / args.steps,
+            "higher_is_better": True,
+            "scaling": "strong" if args.n_total > 0 else "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic: WT901 yaw/gyro-z + 4 wheel rpm per robot (fmskf.synth), 64-tick HBM ring"
+                    + (", one 16-byte fmskf_kf6_record per robot-tick" if krec is not None else ", SoA planes"),
+            "config": {
+                "workload": ("cfg2: 2^20 independent 6-state fp32 KF instances per GPU" if args.n_total <= 0 else
+                             f"cfg4 strong scaling: {n_global} independent 6-state fp32 KF instances over "
+                             f"{world} GPU(s)") +
+                            ", fused correct+predict per tick (fmskf_tick; every ensemble_every-th tick "
+                            + ("fmskf_tick_ensemble_begin: the tick kernel also writes the ensemble record, "
+                               "its fold carried by the next tick, libfmskf's ncclAllGather + copy-out on a side "
+                               "stream, fmskf_ensemble_end two events later)" if args.gather == "native" else
+                               "fmskf_tick_ensemble, which also writes the ensemble record; torch "
+                               "all-gather)"),
+                "instances_per_gpu": n,
+                "global_instances": n_global,
+                "trig": args.trig,
+                "inputs": args.inputs,
+                "ensemble_every": args.ensemble_every,
+                "ensemble": args.ensemble,
+                "gather": args.gather,
+                # the library libfmskf's communicator resolves (a rehearsal names its stand-in)
+                "rccl_library": rccl["library"] if rccl is not None else None,
+                "parallelism": f"instance-sharded x{world}" + (
+                    (", RCCL all-gather of ensemble records" if not gloo else ", gloo all-gather of ensemble records")
+                    if world > 1 else "") + (" (rehearsal: every rank on cuda:0)" if args.same_device else ""),
+            },
+            "full": args.full,
+            "outputs_dumped": dumped,
+        }
+
+    if not args.full:
+        # the plain run ends here: the K timed steps are all it measures
+        if distributed:
+            elapsed, = max_over_ranks([elapsed])
+        out = headline(elapsed)
+        out.update({"timed_region_host": host_split, "ensemble": ensemble_summary(),
+                    "nonfinite_instances": int(eng.get_counters()[0])})
+        if gather_fallback is not None:
+            out["gather_fallback"] = gather_fallback
+        if rccl is not None:
+            out["rccl_ranks"] = rccl["ranks"]
+            out["rccl"] = rccl
+        eng.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if distributed:
+            barrier()
+            dist.destroy_process_group()
+        return
+
     # the same K-step sequence once more between HIP events on the tick stream: the GPU-side
     # duration of the timed region's work on the tick stream (diagnostic; `value` is the wall
     # clock above).  The second event is recorded before the pending results are collected:
@@ -1001,9 +1145,8 @@ def main():
         elapsed, region_ms, tick_ms, planes_ms = max_over_ranks([elapsed, region_ms, tick_ms, planes_ms])
     kern_avg_ms = tick_ms
 
-    total_steps = n_global * args.steps
-    value = total_steps / elapsed
-    ms_per_step = elapsed * 1e3 / args.steps
+    out = headline(elapsed)
+    value, ms_per_step = out["value"], out["ms_per_step"]
 
     # cfg 4 also reports K = 1: the ensemble record (and its all-gather for
     # N > 1) after every tick, over 256 more ticks -- a secondary figure, not `value`
@@ -1048,16 +1191,8 @@ def main():
         cfg4 = run_cfg4_16m()
 
     # ensemble sanity (outside the timed region): fold the last gathered records in rank order
-    last = gathered[(ev_count[0] - 1) % n_events].cpu().numpy() if ev_count[0] else None
-    ens = None
-    if args.gather == "native" and native_stats[0] is not None:
-        # the count is the gathered records' own (the sum of their count rows), not n_global
-        mean, cov, cnt, nrec = native_stats[0]
-        ens = {"count": cnt, "records_folded": nrec, "mean_theta": float(mean[2]), "var_vx": float(cov[9])}
-    elif last is not None:
-        mean, cov = fmskf.ensemble_combine(6, last)
-        ens = {"count": float(last[:, 0].sum()), "mean_theta": float(mean[2]),
-               "var_vx": float(cov[9])}
+    # (the count is the gathered records' own, the sum of their count rows, not n_global)
+    ens = ensemble_summary()
     counters = eng.get_counters()
 
     # --check-ensemble: one more ensemble event through the measured path (fused record or
@@ -1117,43 +1252,7 @@ def main():
 
     bpl = BYTES_PER_STEP["kf6"] * n  # algorithmic bytes per launch (one tick of one GPU)
     achieved = bpl / (kern_avg_ms * 1e-3) / 1e9
-    out = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "strong" if args.n_total > 0 else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic: WT901 yaw/gyro-z + 4 wheel rpm per robot (fmskf.synth), 64-tick HBM ring"
-                + (", one 16-byte fmskf_kf6_record per robot-tick" if krec is not None else ", SoA planes"),
-        "config": {
-            "workload": ("cfg2: 2^20 independent 6-state fp32 KF instances per GPU" if args.n_total <= 0 else
-                         f"cfg4 strong scaling: {n_global} independent 6-state fp32 KF instances over "
-                         f"{world} GPU(s)") +
-                        ", fused correct+predict per tick (fmskf_tick; every ensemble_every-th tick "
-                        + ("fmskf_tick_ensemble_begin: the tick kernel also writes the ensemble record, "
-                           "its fold carried by the next tick, libfmskf's ncclAllGather + copy-out on a side "
-                           "stream, fmskf_ensemble_end two events later)" if args.gather == "native" else
-                           "fmskf_tick_ensemble, which also writes the ensemble record; torch "
-                           "all-gather)"),
-            "instances_per_gpu": n,
-            "global_instances": n_global,
-            "trig": args.trig,
-            "inputs": args.inputs,
-            "ensemble_every": args.ensemble_every,
-            "ensemble": args.ensemble,
-            "gather": args.gather,
-            # the library libfmskf's communicator resolves (a rehearsal names its stand-in)
-            "rccl_library": rccl["library"] if rccl is not None else None,
-            "parallelism": f"instance-sharded x{world}" + (
-                (", RCCL all-gather of ensemble records" if not gloo else ", gloo all-gather of ensemble records")
-                if world > 1 else "") + (" (rehearsal: every rank on cuda:0)" if args.same_device else ""),
-        },
+    out.update({
         "roofline": {
             "bound": "hbm",
             "achieved": achieved,
@@ -1184,7 +1283,7 @@ def main():
         "ensemble_every_1": k1,
         "ensemble": ens,
         "nonfinite_instances": int(counters[0]),
-    }
+    })
     if ens_check is not None:
         out["ensemble_check"] = ens_check
     if gather_fallback is not None:

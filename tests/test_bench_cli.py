@@ -80,3 +80,52 @@ def test_path_byte_models_agree():
     for key, _kernel, rd, wr in pmc_traffic.PATHS:
         if key in committed:
             assert committed[key]["algorithmic_bytes_per_launch"] == (rd + wr) << 20, key
+
+
+def test_dump_indices_fixed_sample():
+    """--dump-outputs keeps every robot of a small fleet and, above bench.DUMP_SAMPLE, the same
+    seeded sample on every call: sorted, distinct, in range, the first and last robot included."""
+    import numpy as np
+    assert np.array_equal(bench.dump_indices(1000), np.arange(1000))
+    assert np.array_equal(bench.dump_indices(bench.DUMP_SAMPLE), np.arange(bench.DUMP_SAMPLE))
+    n = (1 << 20) + 5
+    a, b = bench.dump_indices(n), bench.dump_indices(n)
+    assert np.array_equal(a, b)
+    assert bench.DUMP_SAMPLE - 2 <= a.size <= bench.DUMP_SAMPLE
+    assert a[0] == 0 and a[-1] == n - 1 and np.all(np.diff(a) > 0)
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs: one float32 / float64 .npy per array, the sampled columns of x and P
+    under `robot_index`, the ensemble result beside them, 64 MB at the most for the bench's
+    default fleet of 2^20 robots."""
+    import numpy as np
+    n = bench.DUMP_SAMPLE + 7
+    rng = np.random.default_rng(3)
+    x = rng.standard_normal((6, n)).astype(np.float32)
+    P = rng.standard_normal((21, n)).astype(np.float32)
+    ens = (np.arange(6.0), np.arange(21.0), float(n), 1)
+    d = tmp_path / "dump"
+    shapes = bench.dump_outputs(str(d), x, P, ens)
+    got = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert set(got) == set(shapes) == {"robot_index", "x", "P", "ensemble_mean", "ensemble_cov", "ensemble_count"}
+    idx = got["robot_index"].astype(np.int64)
+    assert np.array_equal(idx, bench.dump_indices(n))
+    assert got["x"].dtype == np.float32 and np.array_equal(got["x"], x[:, idx])
+    assert got["P"].dtype == np.float32 and np.array_equal(got["P"], P[:, idx])
+    assert got["ensemble_mean"].dtype == np.float64 and np.array_equal(got["ensemble_mean"], ens[0])
+    assert np.array_equal(got["ensemble_cov"], ens[1]) and got["ensemble_count"].tolist() == [n]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    # no ensemble event collected yet: the state alone
+    assert set(bench.dump_outputs(str(tmp_path / "d2"), x, P, None)) == {"robot_index", "x", "P"}
+
+
+def test_full_only_options_need_full():
+    """--check-ensemble and --cfg4-16m select parts of the --full run: without --full the command
+    line is refused (exit 2) before torch or a GPU is touched, not silently ignored."""
+    import subprocess
+    for opt in ("--check-ensemble", "--cfg4-16m"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", opt],
+                           capture_output=True, text=True, timeout=60)
+        assert r.returncode == 2 and "--full" in r.stderr, (opt, r.returncode, r.stderr[-500:])

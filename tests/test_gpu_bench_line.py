@@ -1,4 +1,5 @@
-"""The driver's bench command (`python bench.py --gpus 1 --steps 20 --warmup 5`) on the GPU box:
+"""The driver's bench command with every figure (`python bench.py --gpus 1 --steps 20 --warmup 5
+--full`) on the GPU box:
 the one JSON line it prints keeps the contract the round's records are judged on -- BASELINE's
 metric and unit, the cfg 2 workload, whole-job `value` consistent with `ms_per_step`, a
 `roofline` whose `frac` is `achieved / peak` with the PMC `traffic`, the `cpu_baseline` with its
@@ -24,7 +25,8 @@ PATH_BYTES = {"rs_tick_2p20": 140, "rs_tick_2p20_padded_sums": 140, "rs_tick_2p2
 
 
 def test_driver_bench_line_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

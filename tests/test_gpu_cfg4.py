@@ -72,7 +72,7 @@ def test_bench_distributed_path_world1(gather, ensemble):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
            "--steps", "40", "--warmup", "5", "--ensemble-every", "8", "--no-cpu-baseline", "--no-fused",
-           "--no-secondary", "--gather", gather, "--ensemble", ensemble, "--check-ensemble"]
+           "--no-secondary", "--gather", gather, "--ensemble", ensemble, "--check-ensemble", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -95,7 +95,7 @@ def test_bench_spawns_ranks_without_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "20",
            "--warmup", "5", "--n-per-gpu", str(1 << 18), "--ensemble-every", "8", "--no-fused",
-           "--no-secondary", "--check-ensemble", "--cpu-sample-s", "1"]
+           "--no-secondary", "--check-ensemble", "--cpu-sample-s", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -127,7 +127,7 @@ def test_bench_world2_rehearsal_same_gpu(strong, gather, tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
            "--steps", "32", "--warmup", "4", "--ensemble-every", "8", *size,
            "--no-cpu-baseline", "--no-fused", "--no-secondary", "--backend", "gloo", "--same-device",
-           "--check-ensemble", "--gather", gather, "--cfg4-steps", "32"]
+           "--check-ensemble", "--gather", gather, "--cfg4-steps", "32", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -167,7 +167,7 @@ def test_bench_native_gather_falls_back_together(tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
            "--steps", "16", "--warmup", "4", "--ensemble-every", "8", "--n-per-gpu", str(n),
            "--no-cpu-baseline", "--no-fused", "--no-secondary", "--backend", "gloo", "--same-device",
-           "--check-ensemble", "--gather", "native", "--cfg4-steps", "16"]
+           "--check-ensemble", "--gather", "native", "--cfg4-steps", "16", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -26,7 +26,7 @@ OUT=gpurun_out
 mkdir -p "$OUT" build
 STEPS="${STEPS:-smoke tests bench}"
 SQC="SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU GRBM_GUI_ACTIVE"
-DRIVER=(python bench.py --gpus 1 --steps 20 --warmup 5)
+DRIVER=(python bench.py --gpus 1 --steps 20 --warmup 5 --full)
 
 run() {  # name limit cmd...
   local name=$1 limit=$2; shift 2
@@ -114,10 +114,10 @@ for s in $STEPS; do
              done
            done ;;
     dist1) run dist1 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-             --master-port 29531 bench.py --gpus 1 --steps 200 --warmup 20 --no-cpu-baseline --no-fused --no-secondary ;;
+             --master-port 29531 bench.py --gpus 1 --steps 200 --warmup 20 --full --no-cpu-baseline --no-fused --no-secondary ;;
     world4) run world4 600 env FMSKF_RCCL_LIBRARY="$PWD/build/libloopback_rccl.so" LOOPBACK_RCCL_DIR=/tmp \
               LOOPBACK_RCCL_MODE=callback python bench.py --gpus 4 --backend gloo --same-device --gather native \
-              --steps 64 --warmup 8 --no-cpu-baseline --no-fused --no-secondary --cfg4-steps 16 ;;
+              --steps 64 --warmup 8 --full --no-cpu-baseline --no-fused --no-secondary --cfg4-steps 16 ;;
     *) echo "unknown step $s"; exit 2 ;;
   esac
 done
