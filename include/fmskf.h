@@ -192,6 +192,67 @@ int fmskf_tick(fmskf_handle h, const fmskf_tick_inputs *in);
 int fmskf_tick_many(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
                     uint64_t tick_stride);
 
+/* ---- chi-square innovation gate (KF6) ---------------------------------------- */
+/* Off by default: a handle that never sets a gate runs the kernels and computes the bits it
+ * always did, and writes the checkpoints it always wrote.
+ *
+ * With a gate set, every KF6 measurement update -- fmskf_tick, fmskf_correct, each tick of
+ * fmskf_tick_many, whatever the input form (planes, kf6_rec, NULL planes reading the ingest
+ * state, with or without a `valid` mask) -- first forms, per robot, the normalized innovation
+ * squared NIS = y^T S^-1 y from the operands of the update itself: with S = L D L^T, w = L^-1 y
+ * and vw = D^-1 w (y's heading component wrapped to [-pi, pi) as the update wraps it),
+ * nis = w[0]*vw[0], then nis = fma(w[a], vw[a], nis) for a = 1..3 (single rounding, as every fma
+ * of the update).  With `run` the robot's current count of consecutive rejections:
+ *     forced = max_consecutive > 0 && run >= max_consecutive
+ *     apply  = forced || nis <= nis_max          (a NaN NIS is rejected unless forced)
+ * A rejected robot's update is skipped exactly as valid == 0 skips it: x and P are untouched by
+ * the update, and the predict still runs.  An applied update is the ungated update bit for bit.
+ *
+ * Per-robot gate state (fmskf_get_gate):
+ *   status   FMSKF_GATE_* of the last updating call: NONE when it carried no measurement for
+ *            the robot (valid == 0) or none ran yet; FORCED whenever `forced` held, whatever
+ *            the NIS; else ACCEPTED or REJECTED
+ *   run      consecutive rejections, saturating at 255 (so a max_consecutive above 255 never
+ *            forces); 0 after any applied update; unchanged by a call without a measurement
+ *   rejects  total rejections since create / reset / load, saturating at 2^22 - 1
+ *   nis      the last evaluated NIS (applied or not); unchanged when the robot had no
+ *            measurement; 0 before the first
+ * fmskf_tick_many leaves the last tick's status and the last evaluated nis.
+ *
+ * nis_max = +INFINITY with max_consecutive = 0 is monitor-only: nothing is rejected, the state
+ * equals an ungated handle's bit for bit, and NIS is reported.
+ *
+ * KF6 without FMSKF_CFG_COMP_POS only: fmskf_set_gate returns FMSKF_ENOTSUP for RS, EKF9, KF12D
+ * and FMSKF_CFG_COMP_POS handles; FMSKF_EINVAL for a nis_max that is NaN or <= 0, and inside a
+ * graph capture.  Setting a gate on a handle that has none starts from a zero gate state;
+ * changing the thresholds of a set gate keeps the state; NULL turns the gate off.
+ * fmskf_get_gate returns FMSKF_EINVAL while no gate is set.
+ *
+ * fmskf_reset zeroes the gate state and keeps the configuration; fmskf_set_state leaves the gate
+ * state alone; fmskf_save_state writes it as an optional section group when a gate is set (a
+ * gate-less handle's file is unchanged), fmskf_load_state restores it into a gated handle, resets
+ * the gate state when the file has none, and ignores the file's when the handle has no gate.
+ *
+ * The fused forms have no gated counterpart and take the fallbacks they already have: with a
+ * gate set fmskf_isr_tick / fmskf_isr_tick_can run the CAN RX kernel (where it applies), the
+ * gated tick, the control step and the frame (counters [1] and [2] count them as ever), and
+ * fmskf_tick_ensemble / fmskf_tick_ensemble_begin tick gated, then run the stand-alone record.
+ * All of them can be captured (fmskf_graph_begin) like the plain tick.  A gated tick moves
+ * 244 B per robot instead of 232: the gate word read and written, the NIS written. */
+typedef struct fmskf_gate {
+  float nis_max;            /* reject the measurement when !(NIS <= nis_max); +INFINITY: monitor only */
+  uint32_t max_consecutive; /* after this many rejections in a row the next measurement is applied
+                               whatever its NIS (re-acquisition; 0 = never force) */
+} fmskf_gate;
+int fmskf_set_gate(fmskf_handle h, const fmskf_gate *g);   /* NULL = gate off (the default) */
+
+#define FMSKF_GATE_NONE 0      /* no measurement for this robot in the last updating call (valid == 0, or none yet) */
+#define FMSKF_GATE_ACCEPTED 1
+#define FMSKF_GATE_REJECTED 2
+#define FMSKF_GATE_FORCED 3    /* applied because max_consecutive was reached */
+/* all [N]; any pointer may be NULL */
+int fmskf_get_gate(fmskf_handle h, float *nis, uint8_t *status, uint8_t *run, uint32_t *rejects, uint32_t mem);
+
 /* ---- readout --------------------------------------------------------------- */
 /* VEHICLE_CTRL::get_vehicle_pos_m_latest (x m, y m, th rad).  Any pointer may be NULL. */
 int fmskf_get_pose(fmskf_handle h, float *x, float *y, float *th, uint32_t mem);
@@ -247,7 +308,8 @@ int fmskf_get_motor_status(fmskf_handle h, int16_t *microsec_id, int16_t *angle,
  * angle sums / KF6 records, CAN buffers not 16-byte (frames) / 8-byte (stamps) aligned, or a
  * regime where the ISR is not one kernel); [2] = ISRs (fmskf_isr_tick or fmskf_isr_tick_can)
  * that ran as the estimator tick, the control step and the 0x200 frame in three kernels instead
- * of one (KF12D; KF6 / EKF9 past the Infinity Cache).  Results are identical either way; [1] and
+ * of one (KF12D; KF6 / EKF9 past the Infinity Cache; KF6 with a gate set, which also counts in
+ * [1]).  Results are identical either way; [1] and
  * [2] count since create / reset and are not checkpointed. */
 int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters);
 

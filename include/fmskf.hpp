@@ -88,6 +88,14 @@ class Robots {
   // the communicator's size and this rank, as RCCL reports them
   void comm_info(int *world, int *rank) { check(fmskf_comm_info(h_, world, rank), "fmskf_comm_info"); }
 
+  // the chi-square innovation gate of a KF6 fleet (fmskf_set_gate; NULL = off) and its per-robot
+  // readout ([N] each, any pointer may be NULL): the last NIS, FMSKF_GATE_* status, consecutive
+  // and total rejections
+  void set_gate(const fmskf_gate *g) { check(fmskf_set_gate(h_, g), "fmskf_set_gate"); }
+  void get_gate(float *nis, uint8_t *status, uint8_t *run, uint32_t *rejects, uint32_t mem = FMSKF_MEM_HOST) {
+    check(fmskf_get_gate(h_, nis, status, run, rejects, mem), "fmskf_get_gate");
+  }
+
   // VDT::can_tx_routine_intr: correct with the IMU yaw, then VEHICLE_CTRL::update (the
   // odometry / estimator time update, then the control half: interpolators, IK, FF_PI_D),
   // then M_CAN.tx_routine -- reading the device-resident IMU / motor state the ingest calls

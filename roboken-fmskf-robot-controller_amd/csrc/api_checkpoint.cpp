@@ -9,7 +9,10 @@ namespace {
 
 // Checkpoint sections: every per-robot device array of the handle in its device layout (planes
 // at the handle's pitch, tiles), byte for byte.  Groups: 1 estimator (x, P, RS prev sums,
-// counters), 2 IMU ingest, 4 motor ingest, 8 control (state + parameters).
+// counters), 2 IMU ingest, 4 motor ingest, 8 control (state + parameters), 16 the innovation
+// gate's per-robot state (fmskf_set_gate: the gate words, the NIS plane; written only while a gate
+// is set, so a gate-less handle's file is what it always was; the last group of the body, so a
+// handle without a gate loads such a file by not reading it).
 // Format 2 ('FMSKFCK2'): the header records every layout choice a section's bytes depend on
 // (estimator pitch / tile / element size, the motor sums' pitch, the control arrays' tiling
 // and pitch) and a checksum of everything after the header; a file whose layout differs from
@@ -90,6 +93,10 @@ std::vector<CkSection> ck_sections(fmskf_ctx *h, uint32_t groups) {
     v.push_back({c.rpm_prev, (size_t)4 * c.n * 2});
     v.push_back({c.curr, (size_t)4 * c.n * 2});
     v.push_back({c.power, (size_t)c.n});
+  }
+  if (groups & 16) {
+    v.push_back({h->gate.word, (size_t)n * 4});
+    v.push_back({h->gate.nis, (size_t)n * 4});
   }
   return v;
 }
@@ -186,7 +193,8 @@ int fmskf_save_state(fmskf_handle h, const char *path) {
     CkHeader hd{};
     memcpy(hd.magic, kCkMagic, 8);
     ck_layout(h, &hd);
-    hd.groups = 1u | (h->s.imu_reg ? 2u : 0u) | (h->s.m_sum_lo ? 4u : 0u) | (h->ctrl_ready ? 8u : 0u);
+    hd.groups = 1u | (h->s.imu_reg ? 2u : 0u) | (h->s.m_sum_lo ? 4u : 0u) | (h->ctrl_ready ? 8u : 0u) |
+                (h->gate_on ? 16u : 0u);
     rs_prev_materialize(h);  // the file holds the odometry's previous sums in the prev planes
     ctrl_materialize(h);     // and the control step's outputs
     // and the whole WT901 register file in its planes (no row-resident registers)
@@ -242,7 +250,7 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     CkHeader me{};
     ck_layout(h, &me);
     if (hd.abi != me.abi || hd.model != me.model || hd.n != me.n || hd.pitch != me.pitch ||
-        hd.tile != me.tile || hd.elem != me.elem || hd.flags != me.flags || (hd.groups & ~15u))
+        hd.tile != me.tile || hd.elem != me.elem || hd.flags != me.flags || (hd.groups & ~31u))
       fail(FMSKF_EINVAL, "checkpoint does not match this handle (ABI, model, flags, N or layout)");
     if ((hd.groups & 4) && hd.m_pitch != me.m_pitch) fail(FMSKF_EINVAL, "checkpoint motor layout differs");
     if (hd.layout != me.layout)
@@ -276,7 +284,8 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     if (hd.groups & 2) ensure_imu(h);
     if (hd.groups & 4) ensure_motors(h);
     if (hd.groups & 8) ensure_ctrl(h);
-    const std::vector<CkSection> secs = ck_sections(h, hd.groups);
+    // the gate group goes into a handle with a gate set; one without has no gate state to restore
+    const std::vector<CkSection> secs = ck_sections(h, h->gate_on ? hd.groups : hd.groups & ~16u);
     // the section sizes follow from the (validated) layout; check them against the file's
     // before any copy
     const long first = f.tell();
@@ -291,6 +300,7 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     if (!(hd.groups & 2) && h->s.imu_reg) zero_imu(h);
     if (!(hd.groups & 4) && h->s.m_sum_lo) zero_motors(h);
     if (!(hd.groups & 8) && h->ctrl_ready) zero_ctrl(h);
+    if (!(hd.groups & 16)) zero_gate(h);
     h->rs_prev_synced = h->rs_prev_stale = false;  // the prev planes come from the file
     h->ctrl_derived_stale = false;                  // and the control outputs
     hip_check(hipStreamSynchronize(h->stream), "load sync");

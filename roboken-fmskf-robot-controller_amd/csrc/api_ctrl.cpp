@@ -224,7 +224,8 @@ static void isr_launches(fmskf_ctx *h, const TickIn &t, uint8_t *dst) {
   const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
   const CtrlPrm p = ctrl_step_prm(h);
   int fused = (int)hipErrorNotSupported;
-  if (h->cfg.model == FMSKF_MODEL_KF6 && isr_kf6_fused()) {
+  // a gated KF6 has no fused ISR: the gated tick, then the control step and the frame
+  if (h->cfg.model == FMSKF_MODEL_KF6 && isr_kf6_fused() && !h->gate_on) {
     if (!t.rec && !t.rpm) ensure_motors(h);
     fused = launch_isr_kf6(h->s, t, h->kf6, libm, h->ctrl, p, dst, h->stream);
     if (fused != (int)hipErrorNotSupported) launch_check(fused, "isr launch");
@@ -241,7 +242,7 @@ static void isr_launches(fmskf_ctx *h, const TickIn &t, uint8_t *dst) {
     h->isr_ctrl_split++;
     int e = 0;
     switch (h->cfg.model) {
-      case FMSKF_MODEL_KF6: e = launch_kf6(h->s, t, h->kf6, libm, true, true, h->stream); break;
+      case FMSKF_MODEL_KF6: e = kf6_tick_launch(h, t, libm, true, true); break;
       case FMSKF_MODEL_EKF9: e = launch_ekf9(h->s, t, h->ekf9, libm, true, true, h->stream); break;
       case FMSKF_MODEL_KF12D: e = launch_kf12d(h->s, t, h->kf12, true, true, h->stream); break;
     }
@@ -298,7 +299,7 @@ int fmskf_isr_tick_can(fmskf_handle h, const uint8_t *can_frames, const int16_t 
     h->time_begin();
     // one launch where the tick reads the rpm (RS: and the angle sums) the frames carry: no
     // caller rpm / sums / records
-    if (h->cfg.model == FMSKF_MODEL_KF6 && isr_kf6_fused() && !in->kf6_rec && !in->rpm) {
+    if (h->cfg.model == FMSKF_MODEL_KF6 && isr_kf6_fused() && !h->gate_on && !in->kf6_rec && !in->rpm) {
       fused = launch_isr_kf6_can(h->s, t, h->kf6, libm, h->ctrl, ctrl_step_prm(h), dst, (const uint8_t *)f,
                                  (const int16_t *)s, h->cfg.motor_dir, h->stream);
     } else if (h->cfg.model == FMSKF_MODEL_EKF9 && isr_kf6_fused() && !in->rpm) {

@@ -164,6 +164,12 @@ struct fmskf_ctx {
   fmskf::Kf6Params kf6{};
   fmskf::Ekf9Params ekf9{};
   fmskf::Kf12dParams kf12{};
+  // chi-square innovation gate (fmskf_set_gate; KF6 without FMSKF_CFG_COMP_POS): thresholds and
+  // the per-robot gate state planes, allocated when a gate is first set.  While gate_on, every
+  // KF6 measurement update goes through kf6_tick_launch's gated kernels and the fused forms
+  // (ISR, tick + ensemble record) take their fallbacks.
+  bool gate_on = false;
+  fmskf::GateDev gate{};
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
   // call) that ran as the tick, control-step and frame kernels instead of one fused kernel
@@ -383,6 +389,14 @@ TickIn resolve_inputs(fmskf_ctx *h, const fmskf_tick_inputs *in, bool need_upd, 
                       const std::vector<std::pair<const void **, size_t>> *extra = nullptr);
 void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, uint32_t n_ticks,
               uint64_t stride);
+// the KF6 tick / correct / predict launch of a handle: the gated kernels while a gate is set and
+// the call updates, the plain ones otherwise
+inline int kf6_tick_launch(fmskf_ctx *h, const TickIn &t, bool libm, bool upd, bool pred) {
+  if (h->gate_on && upd) return launch_kf6_gate(h->s, t, h->kf6, h->gate, libm, pred, h->stream);
+  return launch_kf6(h->s, t, h->kf6, libm, upd, pred, h->stream);
+}
+// zero the gate state planes (no-op while none are allocated)
+void zero_gate(fmskf_ctx *h);
 void copy_out(fmskf_ctx *h, void *dst, const void *src, size_t bytes, uint32_t mem);
 void copy_planes_out(fmskf_ctx *h, void *dst, const void *src, size_t row, size_t dev_pitch,
                      size_t planes, uint32_t mem);

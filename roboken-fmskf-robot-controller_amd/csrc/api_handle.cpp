@@ -154,6 +154,12 @@ void rs_prev_materialize(fmskf_ctx *h) {
   h->rs_prev_stale = false;
 }
 
+void zero_gate(fmskf_ctx *h) {
+  if (!h->gate.word) return;
+  hip_check(hipMemsetAsync(h->gate.word, 0, h->s.n * 4, h->stream), "reset gate");
+  hip_check(hipMemsetAsync(h->gate.nis, 0, h->s.n * 4, h->stream), "reset gate");
+}
+
 void ensure_motors(fmskf_ctx *h) {
   DevState &s = h->s;
   if (s.m_sum_lo) return;
@@ -223,6 +229,7 @@ void do_reset(fmskf_ctx *h) {
   if (s.xlo) hip_check(hipMemsetAsync(s.xlo, 0, (size_t)kKf6LoRows * pp * 4, st), "reset position low parts");
   if (s.imu_reg) zero_imu(h);
   if (s.m_sum_lo) zero_motors(h);
+  zero_gate(h);  // the gate state restarts, its thresholds stay
   if (h->ctrl_ready) {  // the control objects are static in the firmware too: zero, power off
     const CtrlDev &c = h->ctrl;
     hip_check(hipMemsetAsync(c.ax, 0, (size_t)3 * kAxF * c.pitch * 4, st), "reset ctrl");
@@ -359,7 +366,7 @@ void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, ui
   int e = 0;
   switch (h->cfg.model) {
     case FMSKF_MODEL_RS: e = launch_rs(h->s, t, libm, upd, pred, h->stream); break;
-    case FMSKF_MODEL_KF6: e = launch_kf6(h->s, t, h->kf6, libm, upd, pred, h->stream); break;
+    case FMSKF_MODEL_KF6: e = kf6_tick_launch(h, t, libm, upd, pred); break;
     case FMSKF_MODEL_EKF9: e = launch_ekf9(h->s, t, h->ekf9, libm, upd, pred, h->stream); break;
     case FMSKF_MODEL_KF12D: e = launch_kf12d(h->s, t, h->kf12, upd, pred, h->stream); break;
   }
@@ -809,6 +816,54 @@ int fmskf_set_state(fmskf_handle h, const void *x, const void *p_packed, uint32_
     // compensated positions: a state set from outside restarts every low part (x and P)
     if ((x || p_packed) && h->s.xlo)
       hip_check(hipMemsetAsync(h->s.xlo, 0, (size_t)kKf6LoRows * h->s.pitch * 4, h->stream), "position low parts");
+    finish_out(h, mem);
+  });
+}
+
+int fmskf_set_gate(fmskf_handle h, const fmskf_gate *g) {
+  return guarded([&] {
+    check_handle(h);
+    if (h->cfg.model != FMSKF_MODEL_KF6 || (h->cfg.flags & FMSKF_CFG_COMP_POS))
+      fail(FMSKF_ENOTSUP, "the innovation gate is for KF6 without FMSKF_CFG_COMP_POS");
+    if (h->capturing) fail(FMSKF_EINVAL, "gate changed inside a graph capture");
+    if (!g) {
+      h->gate_on = false;
+      return;
+    }
+    if (!(g->nis_max > 0.0f)) fail(FMSKF_EINVAL, "nis_max must be > 0 (+INFINITY: monitor only)");
+    DeviceGuard dg(h->cfg.device);
+    if (!h->gate.word) {
+      h->gate.word = h->alloc<uint32_t>(h->s.n);
+      h->gate.nis = h->alloc<float>(h->s.n);
+    }
+    if (!h->gate_on) zero_gate(h);  // a newly set gate starts from a zero gate state
+    h->gate.nis_max = g->nis_max;
+    h->gate.max_run = g->max_consecutive;
+    h->gate_on = true;
+  });
+}
+
+int fmskf_get_gate(fmskf_handle h, float *nis, uint8_t *status, uint8_t *run, uint32_t *rejects, uint32_t mem) {
+  return guarded([&] {
+    check_handle(h);
+    if (!h->gate_on) fail(FMSKF_EINVAL, "no gate set (fmskf_set_gate)");
+    if (mem != FMSKF_MEM_HOST && mem != FMSKF_MEM_DEVICE) fail(FMSKF_EINVAL, "bad mem flag");
+    DeviceGuard dg(h->cfg.device);
+    const uint64_t n = h->s.n;
+    copy_out(h, nis, h->gate.nis, n * 4, mem);
+    if (status || run || rejects) {
+      if (mem == FMSKF_MEM_DEVICE) {
+        launch_check(launch_gate_unpack(h->gate.word, n, status, run, rejects, h->stream), "gate readout");
+      } else {  // unpacked into device scratch: rejects [N], status [N], run [N]
+        char *scr = (char *)h->out_for(n * 6);
+        launch_check(launch_gate_unpack(h->gate.word, n, (uint8_t *)scr + 4 * n, (uint8_t *)scr + 5 * n,
+                                        (uint32_t *)scr, h->stream),
+                     "gate readout");
+        copy_out(h, rejects, scr, n * 4, mem);
+        copy_out(h, status, scr + 4 * n, n, mem);
+        copy_out(h, run, scr + 5 * n, n, mem);
+      }
+    }
     finish_out(h, mem);
   });
 }

@@ -159,6 +159,19 @@ struct Kf6Params {
   float *lo;
 };
 constexpr uint32_t kKf6LoRows = 5;
+// The chi-square innovation gate of a KF6 handle (fmskf_set_gate): its configuration and the
+// per-robot gate state, two plain [N] planes read and written by the gated tick kernels alone
+// (kernels_gate.hip; they take it in an argument struct of their own, GateArgs, so the ungated
+// kernels' arguments do not move).  word: bits 0-1 the status (FMSKF_GATE_*), bits 2-9 the run
+// of consecutive rejections, bits 10-31 the total rejections, both saturating; nis: the last
+// evaluated normalized innovation squared.
+struct GateDev {
+  uint32_t *word;
+  float *nis;
+  float nis_max;
+  uint32_t max_run;
+};
+constexpr uint32_t kGateRunShift = 2, kGateRunMax = 255, kGateRejShift = 10, kGateRejMax = (1u << 22) - 1u;
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -371,6 +384,13 @@ int launch_rs(const DevState &s, const TickIn &in, bool libm, bool correct, bool
 // in.ens_blocks set (upd and pred only): *ens_nb receives the grid, i.e. the record count
 int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, bool upd,
                bool pred, hipStream_t st, int *ens_nb = nullptr);
+// the gated KF6 measurement update (kernels_gate.hip), with the predict (pred) or alone; plain
+// state only (no FMSKF_CFG_COMP_POS), no fused ensemble record
+int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,
+                    bool pred, hipStream_t st);
+// the gate words unpacked into status [N], run [N], rejects [N] (device pointers, any may be null)
+int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
+                       hipStream_t st);
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
                 bool pred, hipStream_t st, int *ens_nb = nullptr);
 int launch_kf12d(const DevState &s, const TickIn &in, const Kf12dParams &p, bool upd, bool pred,

@@ -240,11 +240,13 @@ __device__ __forceinline__ void comp_norm(T (&x)[N], T (&P)[NP], T *clo) {
     if ((CPM >> k) & 1ull) th_norm(P[k], clo[slot_p<CXM, CPM>(k)]);
 }
 
-template <class Md, int CI = -1, typename T = typename Md::T, int N = Md::N, int M = Md::M,
-          int NP = Md::N *(Md::N + 1) / 2, unsigned CXM = 0, unsigned long long CPM = 0>
-__device__ __forceinline__ void kf_update(T (&x)[N], T (&P)[NP], const T (&y)[M], const T *R,
-                                          T *lo = nullptr, T *clo = nullptr) {
-  T HP[M][N];
+// The update in two phases, so that a caller can look at the innovation between them (the
+// chi-square gate, kernels_gate.hip): kf_update_factor forms U = L^-1 H P (in HP), D^-1 and
+// w = L^-1 y and touches neither x nor P; kf_update_apply is x += U^T D^-1 w, P -= U^T D^-1 U.
+// kf_update is the two in sequence.
+template <class Md, typename T = typename Md::T, int N = Md::N, int M = Md::M, int NP = Md::N *(Md::N + 1) / 2>
+__device__ __forceinline__ void kf_update_factor(const T (&P)[NP], const T (&y)[M], const T *R, T (&HP)[M][N],
+                                                 T (&dinv)[M], T (&w)[M]) {
 #pragma unroll
   for (int a = 0; a < M; a++) {
 #pragma unroll
@@ -256,7 +258,7 @@ __device__ __forceinline__ void kf_update(T (&x)[N], T (&P)[NP], const T (&y)[M]
   }
   // S = H P H^T + R = L D L^T (L unit lower, no square roots); E[a][b] = L[a][b] D[b]
   // is the pre-division value of the recurrence
-  T L[M][M], E[M][M], dinv[M];
+  T L[M][M], E[M][M];
 #pragma unroll
   for (int a = 0; a < M; a++) {
 #pragma unroll
@@ -275,7 +277,6 @@ __device__ __forceinline__ void kf_update(T (&x)[N], T (&P)[NP], const T (&y)[M]
     }
   }
   // U = L^-1 HP overwrites HP row by row; w = L^-1 y
-  T w[M];
 #pragma unroll
   for (int a = 0; a < M; a++) {
 #pragma unroll
@@ -290,6 +291,12 @@ __device__ __forceinline__ void kf_update(T (&x)[N], T (&P)[NP], const T (&y)[M]
     for (int k = 0; k < a; k++) s = dfma<T>(-L[a][k], w[k], s);
     w[a] = s;
   }
+}
+
+template <class Md, int CI = -1, typename T = typename Md::T, int N = Md::N, int M = Md::M,
+          int NP = Md::N *(Md::N + 1) / 2, unsigned CXM = 0, unsigned long long CPM = 0>
+__device__ __forceinline__ void kf_update_apply(T (&x)[N], T (&P)[NP], const T (&HP)[M][N], const T (&dinv)[M],
+                                                const T (&w)[M], T *lo = nullptr, T *clo = nullptr) {
   // x += U^T (D^-1 w),  P -= U^T (D^-1 U)
   T vw[M], V[M][N];
 #pragma unroll
@@ -319,6 +326,15 @@ __device__ __forceinline__ void kf_update(T (&x)[N], T (&P)[NP], const T (&y)[M]
     }
   }
   comp_norm<CXM, CPM>(x, P, clo);
+}
+
+template <class Md, int CI = -1, typename T = typename Md::T, int N = Md::N, int M = Md::M,
+          int NP = Md::N *(Md::N + 1) / 2, unsigned CXM = 0, unsigned long long CPM = 0>
+__device__ __forceinline__ void kf_update(T (&x)[N], T (&P)[NP], const T (&y)[M], const T *R,
+                                          T *lo = nullptr, T *clo = nullptr) {
+  T HP[M][N], dinv[M], w[M];
+  kf_update_factor<Md, T, N, M, NP>(P, y, R, HP, dinv, w);
+  kf_update_apply<Md, CI, T, N, M, NP, CXM, CPM>(x, P, HP, dinv, w, lo, clo);
 }
 
 // Diagonal R: the measurements are independent, so the joint update equals M scalar updates

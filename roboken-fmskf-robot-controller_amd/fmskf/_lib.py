@@ -28,6 +28,8 @@ TRIG_TABLE512, TRIG_LIBM = 0, 1
 MEM_HOST, MEM_DEVICE = 0, 1
 ABI_VERSION = 3
 CFG_COMP_POS = 1
+# fmskf_get_gate status values (FMSKF_GATE_*)
+GATE_NONE, GATE_ACCEPTED, GATE_REJECTED, GATE_FORCED = range(4)
 
 MODEL_NAMES = {"rs": MODEL_RS, "kf6": MODEL_KF6, "ekf9": MODEL_EKF9, "kf12d": MODEL_KF12D}
 
@@ -69,6 +71,10 @@ class TickInputs(C.Structure):
         ("valid", C.c_void_p),
         ("kf6_rec", C.c_void_p),
     ]
+
+
+class Gate(C.Structure):
+    _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
 
 
 class CtrlParams(C.Structure):
@@ -119,6 +125,8 @@ SIGNATURES = {
     "fmskf_get_state_lo": (C.c_int, [_H, _P, C.POINTER(C.c_uint32), C.c_uint32]),
     "fmskf_set_state_lo": (C.c_int, [_H, _P, C.c_uint32]),
     "fmskf_get_counters": (C.c_int, [_H, _P, C.c_uint32]),
+    "fmskf_set_gate": (C.c_int, [_H, C.POINTER(Gate)]),
+    "fmskf_get_gate": (C.c_int, [_H, _P, _P, _P, _P, C.c_uint32]),
     "fmskf_ensemble_record_len": (C.c_int, [_H, C.POINTER(C.c_uint32)]),
     "fmskf_ensemble_partial": (C.c_int, [_H, _P, C.c_uint32]),
     "fmskf_ensemble_combine": (C.c_int, [C.c_uint32, _P, C.c_uint32, _P, _P]),

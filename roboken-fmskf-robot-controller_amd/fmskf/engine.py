@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (MEM_DEVICE, MEM_HOST, MODEL_EKF9, MODEL_KF6, MODEL_KF12D, MODEL_NAMES,
-                   MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FmskfError,
+                   MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FmskfError, Gate,
                    TickInputs, check, load)
 
 # fmskf_vehicle_info (include/fmskf.h): the VehicleInfo message layout, 84 bytes
@@ -187,6 +187,26 @@ class Engine:
         ps = a.ptr(stamps, np.int16)
         pp = a.ptr(present, np.uint8)
         check(load().fmskf_ingest_can(self.h, pf, ps, pp, a.mem), "ingest_can")
+
+    # ------------------------------------------------------------------ innovation gate
+    def set_gate(self, nis_max=None, max_consecutive=0):
+        """fmskf_set_gate (KF6): reject a measurement whose normalized innovation squared exceeds
+        nis_max (float('inf'): monitor only); after max_consecutive rejections in a row the next
+        measurement is applied whatever its NIS (0: never).  nis_max=None turns the gate off."""
+        if nis_max is None:
+            check(load().fmskf_set_gate(self.h, None), "set_gate")
+            return
+        g = Gate(float(nis_max), int(max_consecutive))
+        check(load().fmskf_set_gate(self.h, C.byref(g)), "set_gate")
+
+    def get_gate(self):
+        """fmskf_get_gate: dict of nis [N] float32, status [N] uint8 (GATE_NONE / ACCEPTED /
+        REJECTED / FORCED), run [N] uint8 (consecutive rejections), rejects [N] uint32 (total)"""
+        out = dict(nis=np.empty(self.n, np.float32), status=np.empty(self.n, np.uint8),
+                   run=np.empty(self.n, np.uint8), rejects=np.empty(self.n, np.uint32))
+        check(load().fmskf_get_gate(self.h, *(a.ctypes.data_as(C.c_void_p) for a in out.values()), MEM_HOST),
+              "get_gate")
+        return out
 
     # ------------------------------------------------------------------ ticks
     def _inputs(self, kw, n_ticks=1, stride=None):

@@ -197,6 +197,31 @@ class Trajectory:
         return fr, stamps
 
 
+def inject_outliers(yaw_deg, rpm, seed: int = SEED, start: int = 20, yaw_share: float = 0.05,
+                    rpm_share: float = 0.05, yaw_max_deg: float = 4.0, rpm_max: int = 30000):
+    """Measurement outliers for the innovation gate (fmskf_set_gate), on copies of KF6 inputs
+    (yaw_deg [T,N] float32, rpm [T,N,4] int16): from tick `start` on, every tick an independent
+    `yaw_share` of the robots reads a yaw off by a uniform draw from +-[0, yaw_max_deg] degrees (a
+    WT901 heading glitch) and another `rpm_share` reads one wheel's rpm off by a uniform draw
+    from [0, rpm_max), clipped to int16 (a slipping wheel).  Returns (yaw_deg, rpm, kind [T,N]
+    uint8: 0 clean, 1 yaw, 2 rpm)."""
+    rng = np.random.default_rng([seed, 0x6A7E])
+    T, n = yaw_deg.shape
+    u = rng.random((T, n))
+    u[:start] = 1.0
+    kind = np.where(u < yaw_share, 1, np.where(u < yaw_share + rpm_share, 2, 0)).astype(np.uint8)
+    yaw = yaw_deg.copy()
+    off = rng.uniform(-yaw_max_deg, yaw_max_deg, (T, n)).astype(np.float32)
+    yaw[kind == 1] += off[kind == 1]
+    out = rpm.copy()
+    wheel = rng.integers(0, 4, (T, n))
+    add = rng.integers(0, rpm_max, (T, n))
+    t_i, r_i = np.nonzero(kind == 2)
+    w_i = wheel[t_i, r_i]
+    out[t_i, r_i, w_i] = np.clip(out[t_i, r_i, w_i].astype(np.int64) + add[t_i, r_i], -32768, 32767).astype(np.int16)
+    return yaw, out, kind
+
+
 def kf6_ring_torch(n: int, ticks: int, seed: int = SEED, device="cuda"):
     """Bench input ring generated directly in HBM (same sensor model as Trajectory,
     vectorised in torch float64 on the GPU; generation is not timed).

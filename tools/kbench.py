@@ -34,6 +34,16 @@ def main():
                     help="KF6 tick with host-resident inputs staged over PCIe per call")
     ap.add_argument("--valid", action="store_true", help="a validity mask per tick (9 in 10 robots valid)")
     ap.add_argument("--comp", action="store_true", help="KF6 with FMSKF_CFG_COMP_POS (compensated positions)")
+    ap.add_argument("--gate", type=float, default=None, metavar="NIS_MAX",
+                    help="KF6 with the innovation gate set (fmskf_set_gate; inf: monitor only, nothing rejected)")
+    ap.add_argument("--gate-consecutive", type=int, default=0, help="--gate: max_consecutive (0: never force)")
+    ap.add_argument("--outliers", type=float, default=0.0, metavar="SHARE",
+                    help="this share of the robots per tick reads a yaw outlier and the same share again an "
+                         "rpm outlier (fmskf.synth.inject_outliers on the input ring; with --gate give a --ring of "
+                         "at least 20 + --ticks, twice --ticks with --ktime: a replayed ring jumps back at its "
+                         "wrap, which the gate rejects)")
+    ap.add_argument("--ktime", action="store_true",
+                    help="--op tick: a second timed loop with per-launch kernel events (fmskf_set_timing)")
     ap.add_argument("--comm", action="store_true",
                     help="--op ens_async: a world-1 RCCL communicator on the handle (fmskf_comm_init)")
     args = ap.parse_args()
@@ -48,9 +58,17 @@ def main():
                      flags=fmskf.CFG_COMP_POS if args.comp else 0)
     if args.comp:
         BYTES["kf6"], BYTES["ekf9"] = 272, 488
+    if args.gate is not None:  # + the gate word read and written, the NIS written
+        e.set_gate(args.gate, args.gate_consecutive)
+        BYTES["kf6"] += 12
     st = torch.cuda.current_stream()
     e.set_stream(st)
     yaw, gz, rpm = kf6_ring_torch(n, R, device=dev)
+    if args.outliers:
+        from fmskf.synth import inject_outliers
+        oy, orpm, _ = inject_outliers(yaw.cpu().numpy(), rpm.cpu().numpy(), start=0, yaw_share=args.outliers,
+                                      rpm_share=args.outliers)
+        yaw, rpm = torch.from_numpy(oy).to(dev), torch.from_numpy(orpm).to(dev)
     if args.pad:  # input planes at a padded per-tick pitch, each array's base staggered
         def padded(t, k):
             T = t.shape[0]
@@ -205,6 +223,10 @@ def main():
         print(json.dumps({"model": args.model, "n": n, "op": "ensemble", "ms_per_call": ms,
                           "x_GBps": e.nx * e.elem * n / (ms * 1e-3) / 1e9}), flush=True)
         return
+    rej0 = int(e.get_gate()["rejects"].sum(dtype=np.int64)) if args.gate is not None else 0
+    # gated: the timed ticks go on where the 20 warm-up ticks stopped (a jump back in the
+    # trajectory is an outlier for most robots)
+    base = 20 if args.gate is not None else 0
     if args.many:
         reps = max(1, args.ticks // args.many)
         sub = {k: v[: args.many] for k, v in many.items()}
@@ -219,17 +241,29 @@ def main():
     else:
         ev0.record(st)
         for k in range(args.ticks):
-            e.tick_prepared(preps[k % R], tick)
+            e.tick_prepared(preps[(base + k) % R], tick)
         ev1.record(st)
         torch.cuda.synchronize()
         ms_tick = ev0.elapsed_time(ev1) / args.ticks
+    extra = {}
+    if args.gate is not None:  # the share of the timed robot-ticks the gate rejected
+        done = reps * args.many if args.many else args.ticks
+        extra = {"gate": args.gate, "outliers": args.outliers,
+                 "rejected_share": (int(e.get_gate()["rejects"].sum(dtype=np.int64)) - rej0) / (n * done)}
+    if args.ktime and not args.many:  # kernel time alone: HIP events around every launch
+        e.set_timing(True)
+        for k in range(args.ticks):
+            e.tick_prepared(preps[(base + args.ticks + k) % R], tick)
+        tot, cnt = e.kernel_time_total()
+        e.set_timing(False)
+        extra["kernel_us_per_tick"] = tot * 1e3 / max(cnt, 1)
     x, P = e.get_state()
     ok = bool(np.isfinite(x).all() and (P is None or np.isfinite(P).all()))
     print(json.dumps({"model": args.model, "n": n, "variant": os.environ.get("FMSKF_KF6_VARIANT", "0"),
                       "valid_mask": args.valid,
                       "op": args.op, "trig": args.trig, "many": args.many, "ms_per_tick": ms_tick,
                       "steps_per_s": n / (ms_tick * 1e-3),
-                      "algo_GBps": BYTES[args.model] * n / (ms_tick * 1e-3) / 1e9, "finite": ok}),
+                      "algo_GBps": BYTES[args.model] * n / (ms_tick * 1e-3) / 1e9, "finite": ok, **extra}),
           flush=True)
 
 
