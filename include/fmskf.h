@@ -253,6 +253,72 @@ int fmskf_set_gate(fmskf_handle h, const fmskf_gate *g);   /* NULL = gate off (t
 /* all [N]; any pointer may be NULL */
 int fmskf_get_gate(fmskf_handle h, float *nis, uint8_t *status, uint8_t *run, uint32_t *rejects, uint32_t mem);
 
+/* ---- absolute pose fixes (KF6, EKF9) ------------------------------------------ */
+/* The tick's measurements are heading, yaw rate and wheel velocity: px and py are open-loop
+ * integrals and their covariance only grows.  fmskf_correct_pose fuses low-rate absolute fixes
+ * (a ceiling camera, UWB, a lidar landmark: 10-30 Hz, a few percent of the fleet per tick) into
+ * the listed robots -- unlike fmskf_set_state, which overwrites x and P.
+ *
+ * Every listed robot gets one measurement update of its current state with H selecting states
+ * 0, 1 (px, py) and, with FMSKF_FIX_HEADING, 2 (theta), and R from `prm`: the model's own update
+ * in its operation order (factorisation S = L D L^T, w = L^-1 y, then x += U^T D^-1 w,
+ * P -= U^T D^-1 U), with NIS = y^T S^-1 y formed between the two phases exactly as the gate above
+ * forms it (nis = w[0]*vw[0], then single-rounded fmas for a = 1..m-1) and
+ *     apply = nis <= prm->nis_max             (+INFINITY: no gate; a NaN NIS never applies)
+ * The heading innovation is wrapped to [-pi, pi) as the model's own update wraps it; the heading
+ * state is left as fmskf_correct leaves it (no extra wrap).  No predict runs, and a robot that is
+ * not listed is neither read nor written.  Compensated states go through their pairs as in the
+ * model's own update: the EKF9 heading (innovation against hi + lo, TwoSum addition,
+ * renormalised), and with FMSKF_CFG_COMP_POS KF6's px, py (innovation against hi + lo), P00, P10,
+ * P11 (TwoSum additions into the low-part rows, renormalised after the update).
+ *
+ * status[k]: FMSKF_GATE_ACCEPTED, FMSKF_GATE_REJECTED or FMSKF_FIX_IGNORED; nis[k]: the evaluated
+ * NIS, 0 for an ignored entry.  Either may be NULL.  A rejected fix leaves the robot's x, P and
+ * low parts bit for bit.  The call keeps nothing between calls: the handle's persistent gate
+ * (fmskf_set_gate) is neither read nor changed, and reset, checkpoints and fmskf_set_state are
+ * unaffected.
+ *
+ * `robot` must be strictly ascending (the gathers of a sorted list coalesce; see DESIGN.md for
+ * the cost model).  A host list (FMSKF_MEM_HOST) is validated before anything is launched:
+ * ascending order, robot < N, and prm (R finite with a positive diagonal, nis_max not NaN and
+ * > 0, no unknown flag bits); a violation returns FMSKF_EINVAL and changes nothing (prm is
+ * validated for a device list too).  A device list (16-byte aligned: each lane reads its fix with
+ * one 16-byte load) cannot be validated on the host: the kernel
+ * ignores any entry with robot >= N and any entry whose robot is not above the entry before it,
+ * reports FMSKF_FIX_IGNORED for it and counts it in fmskf_get_counters slot [3].  A device list
+ * that is unsorted in some other way (say 5, 3, 5) is a caller error: no access leaves the
+ * handle's arrays, but the result for the robots listed twice is unspecified.
+ *
+ * count == 0 is FMSKF_OK with no launch.  fixes / nis / status in host memory are staged like
+ * every other host call; the call is asynchronous on the handle's stream (host outputs: complete
+ * on return), with device pointers it can be captured by fmskf_graph_begin, its launch is
+ * recorded by fmskf_set_timing like a tick-kernel launch, and a state that goes non-finite is
+ * counted in counter [0].
+ *
+ * KF6 (plain and FMSKF_CFG_COMP_POS) and EKF9 (plain); FMSKF_ENOTSUP for RS, KF12D and EKF9
+ * with FMSKF_CFG_COMP_POS. */
+typedef struct fmskf_pose_fix {   /* 16 bytes, one per fixed robot */
+  uint32_t robot;                 /* instance index */
+  float x_m, y_m;                 /* world position, as fmskf_get_pose reports it */
+  float theta_rad;                /* world heading; read only with FMSKF_FIX_HEADING */
+} fmskf_pose_fix;
+
+#define FMSKF_FIX_HEADING 1u      /* z = (px, py, theta), m = 3; otherwise z = (px, py), m = 2 */
+
+typedef struct fmskf_pose_fix_params {
+  double r[6];       /* packed lower triangle of the fix noise, 3x3 (k = i*(i+1)/2 + j); without
+                        FMSKF_FIX_HEADING only the 2x2 block r[0..2] is read */
+  float nis_max;     /* apply a fix only when NIS <= nis_max; +INFINITY = no gate (NaN never applies) */
+  uint32_t flags;    /* FMSKF_FIX_* */
+} fmskf_pose_fix_params;
+
+#define FMSKF_FIX_IGNORED 4       /* status: malformed entry (robot >= N, or not above its predecessor) */
+
+int fmskf_correct_pose(fmskf_handle h, const fmskf_pose_fix *fixes, uint64_t count,
+                       const fmskf_pose_fix_params *prm,
+                       float *nis, uint8_t *status,   /* [count], either may be NULL */
+                       uint32_t mem);
+
 /* ---- readout --------------------------------------------------------------- */
 /* VEHICLE_CTRL::get_vehicle_pos_m_latest (x m, y m, th rad).  Any pointer may be NULL. */
 int fmskf_get_pose(fmskf_handle h, float *x, float *y, float *th, uint32_t mem);
@@ -310,7 +376,9 @@ int fmskf_get_motor_status(fmskf_handle h, int16_t *microsec_id, int16_t *angle,
  * that ran as the estimator tick, the control step and the 0x200 frame in three kernels instead
  * of one (KF12D; KF6 / EKF9 past the Infinity Cache; KF6 with a gate set, which also counts in
  * [1]).  Results are identical either way; [1] and
- * [2] count since create / reset and are not checkpointed. */
+ * [2] count since create / reset and are not checkpointed.  [3] = entries of device fix lists
+ * that fmskf_correct_pose ignored as malformed (FMSKF_FIX_IGNORED); since create / reset, not
+ * checkpointed either. */
 int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters);
 
 /* ---- ensemble statistics (mean / covariance of x across instances) --------- */

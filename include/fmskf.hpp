@@ -96,6 +96,14 @@ class Robots {
     check(fmskf_get_gate(h_, nis, status, run, rejects, mem), "fmskf_get_gate");
   }
 
+  // absolute pose fixes of a sorted subset of the robots (fmskf_correct_pose: a camera / UWB /
+  // landmark callback, between two ISRs): nis / status [count] receive the evaluated NIS and
+  // FMSKF_GATE_ACCEPTED / _REJECTED / FMSKF_FIX_IGNORED, either may be NULL
+  void correct_pose(const fmskf_pose_fix *fixes, uint64_t count, const fmskf_pose_fix_params &prm,
+                    float *nis = nullptr, uint8_t *status = nullptr, uint32_t mem = FMSKF_MEM_HOST) {
+    check(fmskf_correct_pose(h_, fixes, count, &prm, nis, status, mem), "fmskf_correct_pose");
+  }
+
   // VDT::can_tx_routine_intr: correct with the IMU yaw, then VEHICLE_CTRL::update (the
   // odometry / estimator time update, then the control half: interpolators, IK, FF_PI_D),
   // then M_CAN.tx_routine -- reading the device-resident IMU / motor state the ingest calls

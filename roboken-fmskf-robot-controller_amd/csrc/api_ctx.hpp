@@ -6,6 +6,7 @@
 //   api_readout.cpp     readouts of the ingest state, counters, synchronous ensemble records
 //   api_comm.cpp        RCCL (dlopen), the communicator, the asynchronous ensemble exchange
 //   api_ctrl.cpp        control step, CAN TX, the fused ISR, VehicleInfo, timing
+//   api_fix.cpp         fmskf_correct_pose
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -170,6 +171,9 @@ struct fmskf_ctx {
   // (ISR, tick + ensemble record) take their fallbacks.
   bool gate_on = false;
   fmskf::GateDev gate{};
+  // fmskf_correct_pose: malformed entries of device fix lists, counted by the kernel
+  // (fmskf_get_counters [3]); a word of its own, since DevState::counters is checkpointed whole
+  unsigned long long *fix_ignored = nullptr;
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
   // call) that ran as the tick, control-step and frame kernels instead of one fused kernel

@@ -172,6 +172,19 @@ struct GateDev {
   uint32_t max_run;
 };
 constexpr uint32_t kGateRunShift = 2, kGateRunMax = 255, kGateRejShift = 10, kGateRejMax = (1u << 22) - 1u;
+// One fmskf_correct_pose call as its kernel sees it (kernels_fix.hip; an argument struct of its
+// own, like the gate's): the sorted fix list and the optional per-fix outputs (device pointers),
+// the fix noise narrowed to fp32, the call's threshold and the measurement dimension
+struct PoseFixDev {
+  const uint32_t *fixes;  // [count] x 16 B fmskf_pose_fix
+  uint64_t count;
+  float *nis;       // [count] or null
+  uint8_t *status;  // [count] or null
+  unsigned long long *ignored;  // the handle's count of malformed entries (fmskf_get_counters [3])
+  float r[6];       // packed lower triangle, 3 x 3
+  float nis_max;
+  uint32_t m;       // 2: z = (px, py); 3: z = (px, py, theta)
+};
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -391,6 +404,9 @@ int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, con
 // the gate words unpacked into status [N], run [N], rejects [N] (device pointers, any may be null)
 int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
                        hipStream_t st);
+// the absolute pose-fix update of the listed robots (kernels_fix.hip): KF6 (plain and
+// FMSKF_CFG_COMP_POS) and EKF9 (plain); hipErrorNotSupported otherwise
+int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st);
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
                 bool pred, hipStream_t st, int *ens_nb = nullptr);
 int launch_kf12d(const DevState &s, const TickIn &in, const Kf12dParams &p, bool upd, bool pred,

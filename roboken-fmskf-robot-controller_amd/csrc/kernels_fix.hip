@@ -1,0 +1,202 @@
+// kernels_fix.hip -- the absolute pose-fix update (fmskf_correct_pose) of KF6 and EKF9 for gfx950.
+//
+// One lane per fix of a sorted list: the lane reads its 16-byte fmskf_pose_fix and the `robot`
+// word of the entry before it, and -- when the entry is well formed (robot < N and above its
+// predecessor) -- gathers that robot's state rows, runs a measurement update with H = the first
+// M rows of the identity (z = (px, py) or (px, py, theta)) and scatters the rows back.  No
+// predict, and no robot that is not listed is read or written.
+//
+// The update is the tick's, instantiated for another H: kf_update_factor, NIS from w and D^-1 as
+// the chi-square gate forms it (kernels_gate.hip), then kf_update_apply behind the per-lane
+// decision -- with the EKF9's compensated heading (CI = 2, th_add / th_norm) and, for KF6 with
+// FMSKF_CFG_COMP_POS, the position low parts (CXM / CPM) exactly where the models' own updates
+// have them.  A rejected or ignored lane stores nothing.
+//
+// Addressing: the state is tiled [ceil(N / 2048)][rows][2048] (fmskf_internal.hpp st_at) and a
+// wave's robots lie in arbitrary tiles, so the wave-uniform per-chunk descriptors of the tick
+// kernels do not apply.  Each array is one descriptor over the whole array (kernel arguments
+// only, so it stays in SGPRs), the lane's row-0 byte offset is its voffset and row k the scalar
+// offset k * 2048 * 4: one address register per array and the state's cache policy in the aux
+// bits.  An array past 4 GiB (KF6 beyond 51 M robots, EKF9 beyond 23 M) cannot be reached through
+// 32-bit offsets: the BIG form uses 64-bit lane addresses and non-temporal accesses (such a state
+// is always streamed).
+//
+// Cost: the gathers are element-granular.  With `robot` ascending, a wave at density 1 touches
+// each row's 256 contiguous bytes; at one robot in 32 every row load of a lane touches its own
+// 128-byte line (DESIGN.md section 3 has the model and the measured numbers).
+//
+// The kernel takes its own argument struct (FixArgs): nothing is added to the tick kernels'.
+#include "kf6_lane.hpp"
+
+#pragma clang fp contract(off)
+
+namespace fmskf {
+
+struct FixArgs {
+  uint64_t n;      // robots of the handle
+  uint64_t count;  // fixes
+  uint64_t pitch;  // the tiled arrays hold rows x pitch elements
+  float *x, *P;
+  float *thlo;  // EKF9: [N] heading low part
+  float *lo;    // KF6 + FMSKF_CFG_COMP_POS: the tiled low-part rows
+  const uint32_t *fixes;  // [count] x 16 B: robot, x_m, y_m, theta_rad
+  float *nis;             // [count] or null
+  uint8_t *status;        // [count] or null
+  unsigned long long *counters;  // [0]: states that went non-finite
+  unsigned long long *ignored;   // malformed entries
+  float r[6];                    // packed lower triangle of the fix noise (3 x 3)
+  float nis_max;
+};
+
+// H = the first MM rows of the identity
+template <int NX, int MM>
+struct MdFix {
+  using T = float;
+  static constexpr int N = NX, M = MM;
+  __host__ __device__ static constexpr int h1(int a) { return a; }
+  __host__ __device__ static constexpr int h2(int) { return -1; }
+};
+
+// ROWS tiled rows of one robot, addressed per lane
+template <int ROWS, int CP, bool BIG>
+struct FixRows {
+  static constexpr uint32_t W = tile_w<float>();
+  __amdgpu_buffer_rsrc_t r;
+  uint32_t vo;
+  float *p;
+  __device__ __forceinline__ FixRows(float *base, uint64_t pitch, uint32_t robot) {
+    const uint64_t e = (uint64_t)(robot / W) * ((uint64_t)ROWS * W) + robot % W;
+    if constexpr (BIG) {
+      p = base + e;
+    } else {
+      r = rsrc(base, (uint64_t)ROWS * pitch * sizeof(float));
+      vo = (uint32_t)e * 4u;
+    }
+  }
+  __device__ __forceinline__ float ld(int k) const {
+    if constexpr (BIG) return __builtin_nontemporal_load(p + (size_t)k * W);
+    else return ld_f32<CP>(r, vo, k * W * 4);
+  }
+  __device__ __forceinline__ void st(int k, float v) const {
+    if constexpr (BIG) __builtin_nontemporal_store(v, p + (size_t)k * W);
+    else st_f32<st_pol(CP)>(r, vo, k * W * 4, v);
+  }
+};
+
+// NX: 6 (KF6) or 9 (EKF9, with the heading low part); MM: 2 or 3; COMP: KF6's position low parts
+template <int NX, int MM, bool COMP, int CP, bool BIG>
+__global__ __launch_bounds__(kBlock) void k_fix(FixArgs a) {
+  constexpr int NP = NX * (NX + 1) / 2;
+  constexpr bool EKF = NX == 9;
+  static_assert(!(EKF && COMP), "EKF9 with FMSKF_CFG_COMP_POS is not supported");
+  using Md = MdFix<NX, MM>;
+  const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  const bool have = k < a.count;
+  uint32_t robot = 0, prev = 0;
+  float z[3] = {0.f, 0.f, 0.f};
+  if (have) {
+    const uint4 f = reinterpret_cast<const uint4 *>(a.fixes)[k];
+    if (k > 0) prev = a.fixes[(k - 1) * 4];
+    robot = f.x;
+    z[0] = __builtin_bit_cast(float, f.y);
+    z[1] = __builtin_bit_cast(float, f.z);
+    z[2] = __builtin_bit_cast(float, f.w);
+  }
+  const bool ok = have && robot < a.n && (k == 0 || robot > prev);
+  float nis = 0.f;
+  uint32_t status = FMSKF_FIX_IGNORED;
+  if (ok) {
+    const FixRows<NX, CP, BIG> tx(a.x, a.pitch, robot);
+    const FixRows<NP, CP, BIG> tp(a.P, a.pitch, robot);
+    const FixRows<COMP ? (int)kKf6LoRows : 1, CP, BIG> tl(COMP ? a.lo : a.x, a.pitch, robot);
+    float x[NX], P[NP], cl[COMP ? kKf6LoRows : 1] = {}, lo = 0.f;
+#pragma unroll
+    for (int j = 0; j < NX; j++) x[j] = tx.ld(j);
+#pragma unroll
+    for (int j = 0; j < NP; j++) P[j] = tp.ld(j);
+    if constexpr (COMP) {
+#pragma unroll
+      for (int j = 0; j < (int)kKf6LoRows; j++) cl[j] = tl.ld(j);
+    }
+    if constexpr (EKF) {
+      if constexpr (BIG) lo = __builtin_nontemporal_load(a.thlo + robot);
+      else lo = ld_f32<CP>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0);
+    }
+    // y = z - H x: a compensated state is hi + lo (as the EKF9's own heading innovation), the
+    // heading innovation wrapped
+    float y[MM], U[MM][NX], dinv[MM], w[MM];
+    y[0] = COMP ? (z[0] - x[0]) - cl[0] : z[0] - x[0];
+    y[1] = COMP ? (z[1] - x[1]) - cl[1] : z[1] - x[1];
+    if constexpr (MM == 3) y[2] = EKF ? wrap_innov((z[2] - x[2]) - lo) : wrap_innov(z[2] - x[2]);
+    kf_update_factor<Md, float, NX, MM, NP>(P, y, a.r, U, dinv, w);
+    nis = w[0] * (w[0] * dinv[0]);
+#pragma unroll
+    for (int b = 1; b < MM; b++) nis = dfma(w[b], w[b] * dinv[b], nis);
+    const bool apply = nis <= a.nis_max;  // a NaN NIS never applies
+    status = apply ? FMSKF_GATE_ACCEPTED : FMSKF_GATE_REJECTED;
+    if (apply) {
+      if constexpr (EKF) {
+        kf_update_apply<Md, 2, float, NX, MM, NP>(x, P, U, dinv, w, &lo);
+        th_norm(x[2], lo);
+      } else if constexpr (COMP) {
+        kf_update_apply<Md, -1, float, NX, MM, NP, kKf6CXM, kKf6CPM>(x, P, U, dinv, w, nullptr, cl);
+      } else {
+        kf_update_apply<Md, -1, float, NX, MM, NP>(x, P, U, dinv, w);
+      }
+#pragma unroll
+      for (int j = 0; j < NX; j++) tx.st(j, x[j]);
+#pragma unroll
+      for (int j = 0; j < NP; j++) tp.st(j, P[j]);
+      if constexpr (COMP) {
+#pragma unroll
+        for (int j = 0; j < (int)kKf6LoRows; j++) tl.st(j, cl[j]);
+      }
+      if constexpr (EKF) {
+        if constexpr (BIG) __builtin_nontemporal_store(lo, a.thlo + robot);
+        else st_f32<st_pol(CP)>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0, lo);
+      }
+      nan_guard(x, P, a.counters);
+    }
+  }
+  if (have) {
+    if (a.nis) a.nis[k] = nis;
+    if (a.status) a.status[k] = (uint8_t)status;
+  }
+  const unsigned long long bad = __ballot(have && !ok);
+  if (bad && (threadIdx.x & 63) == __builtin_ctzll(bad)) atomicAdd(a.ignored, (unsigned long long)__popcll(bad));
+}
+
+template <int NX, int MM, bool COMP>
+static void launch_fix_m(const FixArgs &a, bool nt, bool big, hipStream_t st) {
+  const dim3 g = grid_for(a.count);
+  if (big) k_fix<NX, MM, COMP, kStateNT, true><<<g, kBlock, 0, st>>>(a);
+  else if (nt) k_fix<NX, MM, COMP, kStateNT, false><<<g, kBlock, 0, st>>>(a);
+  else k_fix<NX, MM, COMP, 0, false><<<g, kBlock, 0, st>>>(a);
+}
+
+int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st) {
+  if (!FMSKF_TILED || !FMSKF_KF6_TILED || s.tile != tile_w<float>()) return (int)hipErrorNotSupported;
+  if (!f.fixes || !f.count || !f.ignored || (f.m != 2 && f.m != 3)) return (int)hipErrorInvalidValue;
+  const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
+  if ((!ekf && s.model != FMSKF_MODEL_KF6) || (ekf && (comp || !s.thlo))) return (int)hipErrorNotSupported;
+  FixArgs a{s.n, f.count, s.pitch, (float *)s.x, (float *)s.P, s.thlo, s.xlo, f.fixes, f.nis, f.status,
+            s.counters, f.ignored, {}, f.nis_max};
+  for (int k = 0; k < 6; k++) a.r[k] = f.r[k];
+  // the state's cache policy as the model's tick launcher chooses it
+  const bool nt = state_nt(ekf ? s.n * 55 * 4 : s.n * (comp ? 128 : 108));
+  // the largest array (P) within reach of a 32-bit byte offset?
+  const bool big = (uint64_t)(ekf ? 45 : 21) * s.pitch * sizeof(float) > 0xFFFFFFFFull;
+  if (ekf) {
+    if (f.m == 3) launch_fix_m<9, 3, false>(a, nt, big, st);
+    else launch_fix_m<9, 2, false>(a, nt, big, st);
+  } else if (comp) {
+    if (f.m == 3) launch_fix_m<6, 3, true>(a, nt, big, st);
+    else launch_fix_m<6, 2, true>(a, nt, big, st);
+  } else {
+    if (f.m == 3) launch_fix_m<6, 3, false>(a, nt, big, st);
+    else launch_fix_m<6, 2, false>(a, nt, big, st);
+  }
+  return (int)hipGetLastError();
+}
+
+}  // namespace fmskf

@@ -30,6 +30,9 @@ ABI_VERSION = 3
 CFG_COMP_POS = 1
 # fmskf_get_gate status values (FMSKF_GATE_*)
 GATE_NONE, GATE_ACCEPTED, GATE_REJECTED, GATE_FORCED = range(4)
+# fmskf_correct_pose: FMSKF_FIX_HEADING (flag), FMSKF_FIX_IGNORED (status of a malformed entry)
+FIX_HEADING = 1
+FIX_IGNORED = 4
 
 MODEL_NAMES = {"rs": MODEL_RS, "kf6": MODEL_KF6, "ekf9": MODEL_EKF9, "kf12d": MODEL_KF12D}
 
@@ -75,6 +78,14 @@ class TickInputs(C.Structure):
 
 class Gate(C.Structure):
     _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
+
+
+class PoseFix(C.Structure):
+    _fields_ = [("robot", C.c_uint32), ("x_m", C.c_float), ("y_m", C.c_float), ("theta_rad", C.c_float)]
+
+
+class PoseFixParams(C.Structure):
+    _fields_ = [("r", C.c_double * 6), ("nis_max", C.c_float), ("flags", C.c_uint32)]
 
 
 class CtrlParams(C.Structure):
@@ -127,6 +138,7 @@ SIGNATURES = {
     "fmskf_get_counters": (C.c_int, [_H, _P, C.c_uint32]),
     "fmskf_set_gate": (C.c_int, [_H, C.POINTER(Gate)]),
     "fmskf_get_gate": (C.c_int, [_H, _P, _P, _P, _P, C.c_uint32]),
+    "fmskf_correct_pose": (C.c_int, [_H, _P, C.c_uint64, C.POINTER(PoseFixParams), _P, _P, C.c_uint32]),
     "fmskf_ensemble_record_len": (C.c_int, [_H, C.POINTER(C.c_uint32)]),
     "fmskf_ensemble_partial": (C.c_int, [_H, _P, C.c_uint32]),
     "fmskf_ensemble_combine": (C.c_int, [C.c_uint32, _P, C.c_uint32, _P, _P]),

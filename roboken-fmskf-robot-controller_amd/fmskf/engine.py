@@ -13,8 +13,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (MEM_DEVICE, MEM_HOST, MODEL_EKF9, MODEL_KF6, MODEL_KF12D, MODEL_NAMES,
-                   MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FmskfError, Gate,
-                   TickInputs, check, load)
+                   MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FIX_HEADING, FmskfError,
+                   Gate, PoseFixParams, TickInputs, check, load)
 
 # fmskf_vehicle_info (include/fmskf.h): the VehicleInfo message layout, 84 bytes
 VEHICLE_INFO_DTYPE = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("pos_theta", "<f4"),
@@ -25,6 +25,9 @@ VEHICLE_INFO_DTYPE = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("pos_theta",
 
 # fmskf_kf6_record (include/fmskf.h): one robot's KF6 tick record, 16 bytes
 KF6_RECORD_DTYPE = np.dtype([("yaw_deg", "<f4"), ("gyro_z_dps", "<f4"), ("rpm", "<i2", 4)])
+
+# fmskf_pose_fix (include/fmskf.h): one absolute pose fix, 16 bytes
+POSE_FIX_DTYPE = np.dtype([("robot", "<u4"), ("x_m", "<f4"), ("y_m", "<f4"), ("theta_rad", "<f4")])
 
 _DTYPES = {
     "yaw_deg": np.float32, "gyro_z_dps": np.float32, "rpm": np.int16, "angle_sum": np.int64,
@@ -52,6 +55,42 @@ def kf6_records(yaw_deg, gyro_z_dps, rpm):
     rec["gyro_z_dps"] = gyro_z_dps
     rec["rpm"] = rpm
     return rec
+
+
+def pose_fix_records(robot, x, y, theta=None):
+    """Pack absolute pose fixes ([count] robot indices, strictly ascending; x, y in metres,
+    theta in radians or None; all numpy or all torch device tensors) into fmskf_pose_fix's:
+    numpy -> [count] POSE_FIX_DTYPE, torch -> [count, 4] int32."""
+    if _is_torch(robot):
+        import torch
+        rec = torch.zeros((robot.shape[0], 4), dtype=torch.int32, device=robot.device)
+        rec[:, 0] = robot.to(torch.int32)  # the low 32 bits
+        for k, v in ((1, x), (2, y), (3, theta)):
+            if v is not None:
+                rec[:, k] = v.to(torch.float32).contiguous().view(torch.int32)
+        return rec
+    rec = np.zeros(np.shape(robot), POSE_FIX_DTYPE)
+    rec["robot"] = robot
+    rec["x_m"] = x
+    rec["y_m"] = y
+    if theta is not None:
+        rec["theta_rad"] = theta
+    return rec
+
+
+def _fix_noise(r):
+    """packed lower triangle [6] of the 3x3 fix noise from a scalar variance, a diagonal [3],
+    the packed triangle [6] or the matrix [3, 3]"""
+    v = np.asarray(r, np.float64)
+    if v.ndim == 0:
+        v = np.full(3, float(v))
+    if v.shape == (3, 3):
+        return [v[i, j] for i in range(3) for j in range(i + 1)]
+    if v.shape == (3,):
+        return [v[0], 0.0, v[1], 0.0, 0.0, v[2]]
+    if v.shape == (6,):
+        return list(v)
+    raise ValueError(f"fix noise: shape {v.shape}, want (), (3,), (6,) or (3, 3)")
 
 
 def _is_torch(a) -> bool:
@@ -207,6 +246,55 @@ class Engine:
         check(load().fmskf_get_gate(self.h, *(a.ctypes.data_as(C.c_void_p) for a in out.values()), MEM_HOST),
               "get_gate")
         return out
+
+    # ------------------------------------------------------------------ absolute pose fixes
+    def correct_pose(self, robot=None, x=None, y=None, theta=None, r=1e-4, nis_max=float("inf"), out=False,
+                     fixes=None, heading=None):
+        """fmskf_correct_pose: fuse absolute fixes into the listed robots (KF6, EKF9).  `robot`
+        [count] strictly ascending with x, y (and theta: the heading is then measured too), numpy
+        arrays or torch device tensors; or `fixes`, records packed by pose_fix_records(), with `heading`
+        saying whether theta_rad is read.  r: the fix noise (a variance, its diagonal [3], the
+        packed triangle [6] or [3, 3]); nis_max: apply a fix only when its NIS <= nis_max.
+        out=True returns (nis [count] float32, status [count] uint8: GATE_ACCEPTED / GATE_REJECTED
+        / FIX_IGNORED) as numpy arrays (host list) or torch tensors (device list); out=(nis,
+        status) writes into the given device tensors (a call that is captured)."""
+        if fixes is None:
+            fixes = pose_fix_records(robot, x, y, theta)
+            if heading is None:
+                heading = theta is not None
+        prm = PoseFixParams()
+        for k, v in enumerate(_fix_noise(r)):
+            prm.r[k] = float(v)
+        prm.nis_max = float(nis_max)
+        prm.flags = FIX_HEADING if heading else 0
+        a = _Args()
+        if _is_torch(fixes):
+            if str(fixes.dtype) != "torch.int32" or fixes.dim() != 2 or fixes.shape[1] != 4:
+                raise TypeError("fixes: want a [count, 4] int32 tensor (pose_fix_records)")
+            count = int(fixes.shape[0])
+            pf = a.ptr(fixes)
+        else:
+            fixes = np.ascontiguousarray(fixes)
+            if fixes.dtype != POSE_FIX_DTYPE:
+                raise TypeError("fixes: want POSE_FIX_DTYPE records (pose_fix_records)")
+            count = int(fixes.size)
+            pf = a.ptr(fixes.view(np.uint32))
+        mem = MEM_HOST if a.mem is None else a.mem
+        nis = status = None
+        if isinstance(out, tuple):
+            nis, status = out
+            if mem != MEM_DEVICE:
+                raise TypeError("out tensors go with a device fix list")
+        elif out and mem == MEM_DEVICE:
+            import torch
+            nis = torch.zeros(count, dtype=torch.float32, device=fixes.device)
+            status = torch.zeros(count, dtype=torch.uint8, device=fixes.device)
+        elif out:
+            nis, status = np.zeros(count, np.float32), np.zeros(count, np.uint8)
+        pn = a.ptr(nis) if nis is not None else None
+        ps = a.ptr(status) if status is not None else None
+        check(load().fmskf_correct_pose(self.h, pf, count, C.byref(prm), pn, ps, mem), "correct_pose")
+        return (nis, status) if nis is not None or status is not None else None
 
     # ------------------------------------------------------------------ ticks
     def _inputs(self, kw, n_ticks=1, stride=None):
@@ -667,5 +755,5 @@ def default_config(model="kf6", n=1) -> Config:
     return cfg
 
 
-__all__ = ["Engine", "ensemble_combine", "default_config", "comm_unique_id", "VEHICLE_INFO_DTYPE", "MODEL_RS", "MODEL_KF6", "MODEL_EKF9",
+__all__ = ["Engine", "pose_fix_records", "POSE_FIX_DTYPE", "ensemble_combine", "default_config", "comm_unique_id", "VEHICLE_INFO_DTYPE", "MODEL_RS", "MODEL_KF6", "MODEL_EKF9",
            "MODEL_KF12D", "TRIG_TABLE512", "TRIG_LIBM", "_lib"]

@@ -222,6 +222,38 @@ def inject_outliers(yaw_deg, rpm, seed: int = SEED, start: int = 20, yaw_share: 
     return yaw, out, kind
 
 
+def pose_fixes(traj, t, every: int = 32, start: int = 8, sigma: float = 1e-2, outlier_share: float = 0.05,
+               outlier_start: int = 40, seed: int = SEED):
+    """Absolute pose fixes (a ceiling camera, UWB: fmskf_correct_pose) for the call made before
+    tick `t` of `traj`: the robots with (i + t) % every == 0 for t >= start (none before), so every
+    robot is seen once per `every` ticks and a tick carries 1 / every of the fleet.  The state at
+    that point has been predicted t times: the truth is traj.px[t - 1], traj.py[t - 1], traj.th[t];
+    each component reads it with Gaussian noise `sigma` (m, m, rad).  From tick `outlier_start` on an
+    independent `outlier_share` of the fixes is displaced by 0.5 - 2 m in a uniformly drawn
+    direction (a wrong association).  Outliers must not start before every robot has had a fix:
+    against the initial position variance a 2 m error is unremarkable, it would be accepted, and
+    the robot would then reject every good fix after it.
+    Returns (robot [count] uint32 ascending, x [count] f32, y, theta, outlier [count] bool)."""
+    n = traj.n
+    if t < start or t < 1:
+        e = np.zeros(0, np.float32)
+        return np.zeros(0, np.uint32), e, e.copy(), e.copy(), np.zeros(0, bool)
+    robot = np.arange((-t) % every, n, every, dtype=np.int64)
+    rng = np.random.default_rng([seed, 0x706F7365, t])
+    c = robot.size
+    nz = rng.normal(0.0, sigma, (3, c))
+    x = traj.px[t - 1, robot] + nz[0]
+    y = traj.py[t - 1, robot] + nz[1]
+    th = traj.th[t, robot] + nz[2]
+    u = rng.random(c)
+    dist = rng.uniform(0.5, 2.0, c)
+    ang = rng.uniform(0.0, 2 * np.pi, c)
+    outlier = (u < outlier_share) & (t >= outlier_start)
+    x = np.where(outlier, x + dist * np.cos(ang), x)
+    y = np.where(outlier, y + dist * np.sin(ang), y)
+    return robot.astype(np.uint32), x.astype(np.float32), y.astype(np.float32), th.astype(np.float32), outlier
+
+
 def kf6_ring_torch(n: int, ticks: int, seed: int = SEED, device="cuda"):
     """Bench input ring generated directly in HBM (same sensor model as Trajectory,
     vectorised in torch float64 on the GPU; generation is not timed).

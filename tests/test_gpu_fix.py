@@ -1,0 +1,530 @@
+"""The absolute pose-fix update (fmskf_correct_pose; csrc/kernels_fix.hip) on the GPU: a single
+update of KF6, KF6 + FMSKF_CFG_COMP_POS and EKF9 against the float64 update of the same fp32
+pre-state (tests/fix_ref.py), robots that are not listed or whose fix is rejected bit for bit
+untouched, the closed loop against the float64 reference, every calling form against every other
+bit for bit, the edges, and that nothing else of a handle moves."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+import fmskf
+from fmskf import Engine
+from fmskf.synth import Trajectory
+
+import fix_ref
+from fix_ref import NIS_MAX
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N = 4113      # not a multiple of 256, three 2048-wide tiles
+WARM = 50     # ticks before the single update
+ACC, REJ, IGN = fmskf.GATE_ACCEPTED, fmskf.GATE_REJECTED, fmskf.FIX_IGNORED
+MODELS = {"kf6": ("kf6", 0), "kf6comp": ("kf6", fmskf.CFG_COMP_POS), "ekf9": ("ekf9", 0)}
+# The largest deviations of test 1 measured on an MI355X (profiles/pose_fix.json,
+# "single_update": per model and m the largest |GPU - float64| over the 129 listed robots in x, in
+# P and in NIS relative to max(NIS, 1)); the test asserts ten times the measured value.
+with open(os.path.join(ROOT, "profiles", "pose_fix.json")) as _f:
+    MEASURED = json.load(_f)["single_update"]
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def _snapshot(e):
+    x, P = e.get_state()
+    lo = e.get_state_lo()
+    return x, P, lo
+
+
+def _same(a, b, what, cols=None):
+    for name, u, v in zip(("x", "P", "lo"), a, b):
+        if u is None and v is None:
+            continue
+        if cols is not None:
+            u, v = u[:, cols], v[:, cols]
+        assert np.array_equal(_bits(u), _bits(v)), f"{what}: {name}"
+
+
+def _engine(key, n=N, **kw):
+    model, flags = MODELS[key]
+    return Engine(model, n, flags=flags, **kw)
+
+
+_TRAJ = {}
+
+
+def _warm(orc, key, n=N, T=WARM, seed=77):
+    """(trajectory, tick keywords) of the warm-up run, shared"""
+    model = MODELS[key][0]
+    k = (model, n, T, seed)
+    if k not in _TRAJ:
+        tr = Trajectory(n, T + 1, seed=seed)
+        _TRAJ[k] = (tr, fix_ref.model_inputs(orc, model, tr)[0])
+    return _TRAJ[k]
+
+
+def _warmed(orc, key, n=N, T=WARM, **kw):
+    tr, tk = _warm(orc, key, n, T)
+    e = _engine(key, n, **kw)
+    for t in range(T):
+        e.tick(**tk[t])
+    return e, tr
+
+
+def _list129(n=N):
+    """129 robots ascending, the tile edges among them"""
+    rng = np.random.default_rng(129)
+    must = np.array([0, 2047, 2048, n - 1])
+    rest = rng.choice(np.setdiff1d(np.arange(n), must), 125, replace=False)
+    return np.sort(np.concatenate([must, rest])).astype(np.uint32)
+
+
+def _fixes_for(tr, robot, t=WARM, sigma=0.3, seed=3):
+    """fixes of `robot` for the call before tick t: the truth with Gaussian noise sigma"""
+    rng = np.random.default_rng(seed)
+    r = robot.astype(np.int64)
+    nz = rng.normal(0.0, sigma, (3, r.size))
+    return (robot, (tr.px[t - 1, r] + nz[0]).astype(np.float32), (tr.py[t - 1, r] + nz[1]).astype(np.float32),
+            (tr.th[t, r] + 0.1 * nz[2]).astype(np.float32))
+
+
+def _f64_state(snap, model):
+    """x [N, n], P [N, n, n] float64 of a snapshot, compensated entries as hi + lo"""
+    x, P, lo = snap
+    x64, P64 = x.astype(np.float64), P.astype(np.float64)
+    if lo is not None:
+        lo = lo.astype(np.float64)
+        if model == "ekf9":
+            x64[2] += lo[0]
+        else:  # px, py, P00, P10, P11
+            x64[0] += lo[0]
+            x64[1] += lo[1]
+            P64[0] += lo[2]
+            P64[1] += lo[3]
+            P64[2] += lo[4]
+    return fix_ref.unpack_state(x64, P64)
+
+
+def single_update(orc, key, m):
+    """One call of 129 fixes after WARM ticks against the float64 update of the same pre-state:
+    dict of the largest deviations (x, P, nis) and the post-update position block"""
+    model = MODELS[key][0]
+    e, tr = _warmed(orc, key)
+    with e:
+        robot = _list129()
+        fx = _fixes_for(tr, robot)
+        pre = _snapshot(e)
+        nis, status = e.correct_pose(*fx[:3], fx[3] if m == 3 else None, r=fix_ref.R_FIX, out=True)
+        post = _snapshot(e)
+        assert e.get_counters()[0] == 0 and e.get_counters()[3] == 0
+    assert np.all(status == ACC)
+    r = robot.astype(np.int64)
+    x0, P0 = _f64_state(pre, model)
+    z = np.stack([a.astype(np.float64) for a in fx[1:1 + m]], axis=1)
+    xr, Pr, nr, ar = fix_ref.fix_update_f64(x0[r], P0[r], z, m, np.inf)
+    xg, Pg = _f64_state(post, model)
+    others = np.setdiff1d(np.arange(N), r)
+    _same(pre, post, f"{key} m={m}: robots not listed", others)
+    dev = dict(x=float(np.abs(xg[r] - xr).max()), P=float(np.abs(Pg[r] - Pr).max()),
+               nis=float((np.abs(nis - nr) / np.maximum(nr, 1.0)).max()))
+    P00, P10, P11 = (post[1][k][r].astype(np.float64) for k in range(3))
+    return dev, (P00, P10, P11), (pre[1][0][r] / fix_ref.R_FIX)
+
+
+# ---------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("m", [2, 3])
+@pytest.mark.parametrize("key", list(MODELS))
+def test_single_update_against_float64(orc, key, m):
+    """x, P and NIS of the 129 listed robots (0, 2047, 2048 and N - 1 among them) after one call
+    against the float64 update of the same fp32 pre-state, within ten times the deviation measured
+    on an MI355X (profiles/pose_fix.json); the position block stays positive definite at the first
+    fix, where P00 / R = 1e4"""
+    dev, (P00, P10, P11), ratio = single_update(orc, key, m)
+    tol = MEASURED[key][str(m)]
+    print(f"{key} m={m}: deviations {dev}; measured {tol}; first-fix P00/R {ratio.min():.3g}..{ratio.max():.3g}; "
+          f"P00 after >= {P00.min():.3e}")
+    assert ratio.min() > 5e3
+    assert np.all(P00 > 0) and np.all(P11 > 0) and np.all(P00 * P11 - P10 * P10 > 0)
+    for k in ("x", "P", "nis"):
+        assert dev[k] <= 10 * tol[k], (k, dev[k], tol[k])
+
+
+# ---------------------------------------------------------------------------- 2
+@pytest.mark.parametrize("m", [2, 3])
+@pytest.mark.parametrize("key", list(MODELS))
+def test_unlisted_and_rejected_robots_untouched(orc, key, m):
+    """every robot that is not listed is bit-identical before and after a call (x, P, low parts),
+    and so is every robot whose fix is rejected: a 5 m offset at nis_max = 13.82 once the
+    covariance has come down"""
+    e, tr = _warmed(orc, key)
+    with e:
+        robot = _list129()
+        fx = _fixes_for(tr, robot, sigma=0.01)
+        th = fx[3] if m == 3 else None
+        s0 = _snapshot(e)
+        _, st = e.correct_pose(fx[0], fx[1], fx[2], th, r=fix_ref.R_FIX, out=True)
+        assert np.all(st == ACC)
+        s1 = _snapshot(e)
+        others = np.setdiff1d(np.arange(N), robot.astype(np.int64))
+        _same(s0, s1, "not listed", others)
+        assert not np.array_equal(_bits(s0[1][:, robot]), _bits(s1[1][:, robot]))
+        nis, st = e.correct_pose(fx[0], fx[1] + np.float32(5.0), fx[2], th, r=fix_ref.R_FIX, nis_max=13.82, out=True)
+        assert np.all(st == REJ) and np.all(nis > 13.82)
+        _same(s1, _snapshot(e), "rejected")
+        # half of them off: only the good half moves
+        off = np.where(np.arange(robot.size) % 2 == 0, np.float32(5.0), np.float32(0.0)).astype(np.float32)
+        nis, st = e.correct_pose(fx[0], fx[1] + off, fx[2], th, r=fix_ref.R_FIX, nis_max=13.82, out=True)
+        assert np.array_equal(st, np.where(off > 0, REJ, ACC))
+        s3 = _snapshot(e)
+        _same(s1, s3, "rejected half", np.concatenate([others, robot[off > 0].astype(np.int64)]))
+        assert e.get_counters()[3] == 0
+
+
+# ---------------------------------------------------------------------------- 3
+@pytest.mark.parametrize("key,m", [("kf6", 2), ("kf6", 3), ("ekf9", 3)])
+def test_closed_loop_against_float64(orc, key, m):
+    """4096 robots x 400 ticks with the pose_fixes defaults: every decision equals the float64
+    reference's outside the band, the final position error against the truth is at most twice the
+    reference's own maximum, and without the calls the same run's P00 is larger for every robot"""
+    ref = fix_ref.closed_loop(orc, key, m)
+    tr, n, T = ref["traj"], fix_ref.N_LOOP, fix_ref.T_LOOP
+    differ = compared = 0
+    with _engine(key, n) as e, _engine(key, n) as plain:
+        for t in range(T):
+            robot, x, y, th, _ = ref["fixes"][t]
+            if robot.size:
+                nis, st = e.correct_pose(robot, x, y, th if m == 3 else None, r=fix_ref.R_FIX, nis_max=NIS_MAX[m], out=True)
+                assert not np.any(st == IGN)
+                cmp_ = ~fix_ref.in_band(ref["nis"][t], m)
+                differ += int(np.count_nonzero((st == ACC)[cmp_] != ref["apply"][t][cmp_]))
+                compared += int(np.count_nonzero(cmp_))
+            e.tick(**ref["kw"][t])
+            plain.tick(**ref["kw"][t])
+        x, P = e.get_state()
+        _, Pp = plain.get_state()
+        assert e.get_counters()[0] == 0 and e.get_counters()[3] == 0
+    err = np.hypot(x[0] - tr.px[T - 1], x[1] - tr.py[T - 1])
+    print(f"{key} m={m}: decisions compared {compared}, different {differ}; final position error max "
+          f"{err.max():.3e} m (float64 reference {ref['err'].max():.3e} m); P00 max {P[0].max():.3e} with, "
+          f"min {Pp[0].min():.3e} without")
+    assert compared >= 50000 and differ == 0
+    assert err.max() <= 2 * ref["err"].max()
+    assert np.all(Pp[0] > P[0])
+
+
+# ---------------------------------------------------------------------------- 4
+def _call_forms(e, fx, m, form, torch):
+    """the same fixes in another calling form"""
+    th = fx[3] if m == 3 else None
+    kw = dict(r=fix_ref.R_FIX, nis_max=NIS_MAX[m])
+    if form == "host":
+        return e.correct_pose(fx[0], fx[1], fx[2], th, out=True, **kw)
+    rec = torch.from_numpy(fmskf.pose_fix_records(*fx[:3], th).view(np.int32).reshape(-1, 4)).cuda()
+    if form == "device":
+        nis, st = e.correct_pose(fixes=rec, heading=m == 3, out=True, **kw)
+        return nis.cpu().numpy(), st.cpu().numpy()
+    if form == "device_null":
+        assert e.correct_pose(fixes=rec, heading=m == 3, **kw) is None
+        return None
+    if form == "host_null":
+        assert e.correct_pose(fx[0], fx[1], fx[2], th, **kw) is None
+        return None
+    if form == "split":
+        k = 47
+        a = e.correct_pose(fixes=rec[:k].contiguous(), heading=m == 3, out=True, **kw)
+        b = e.correct_pose(fixes=rec[k:].contiguous(), heading=m == 3, out=True, **kw)
+        return torch.cat([a[0], b[0]]).cpu().numpy(), torch.cat([a[1], b[1]]).cpu().numpy()
+    if form == "graph":
+        nis = torch.zeros(rec.shape[0], dtype=torch.float32, device="cuda")
+        st = torch.zeros(rec.shape[0], dtype=torch.uint8, device="cuda")
+        e.graph_begin()
+        e.correct_pose(fixes=rec, heading=m == 3, out=(nis, st), **kw)
+        e.graph_end()
+        e.graph_launch(1)
+        e.sync()
+        return nis.cpu().numpy(), st.cpu().numpy()
+    raise ValueError(form)
+
+
+@pytest.mark.parametrize("key,m", [("kf6", 3), ("kf6comp", 2), ("ekf9", 3)])
+def test_forms_agree_bit_for_bit(orc, key, m):
+    """host list, device list, outputs requested or NULL, one call or two calls split at an
+    arbitrary point, and a captured-and-replayed call: the same state, NIS and status bits (a
+    third of the fixes are 5 m off, so both decisions occur)"""
+    import torch
+    tr, tk = _warm(orc, key)
+    robot = _list129()
+    good = _fixes_for(tr, robot, sigma=0.01)
+    off = np.where(np.arange(robot.size) % 3 == 0, np.float32(5.0), np.float32(0.0)).astype(np.float32)
+    second = (good[0], good[1] + off, good[2], good[3])
+    st_ = torch.cuda.Stream()
+    results = {}
+    with torch.cuda.stream(st_):
+        for form in ("host", "device", "device_null", "host_null", "split", "graph"):
+            with _engine(key) as e:
+                e.set_stream(st_)
+                for t in range(WARM):
+                    e.tick(**tk[t])
+                e.correct_pose(*good[:3], good[3] if m == 3 else None, r=fix_ref.R_FIX)  # covariance down
+                out = _call_forms(e, second, m, form, torch)
+                results[form] = (_snapshot(e), out)
+    base, out0 = results["host"]
+    assert np.any(out0[1] == REJ) and np.any(out0[1] == ACC)
+    for form, (snap, out) in results.items():
+        _same(base, snap, form)
+        if out is not None:
+            assert np.array_equal(_bits(out[0]), _bits(out0[0])), f"{form}: nis"
+            assert np.array_equal(out[1], out0[1]), f"{form}: status"
+
+
+@pytest.mark.parametrize("key", ["kf6", "ekf9"])
+def test_whole_fleet_against_strided_calls(orc, key):
+    """count == N in one call against the same fixes in 32 strided calls (robots k, k + 32, ...)"""
+    tr, tk = _warm(orc, key)
+    robot = np.arange(N, dtype=np.uint32)
+    fx = _fixes_for(tr, robot, sigma=0.05)
+    with _engine(key) as a, _engine(key) as b:
+        for t in range(WARM):
+            a.tick(**tk[t])
+            b.tick(**tk[t])
+        nis_a, st_a = a.correct_pose(*fx, r=fix_ref.R_FIX, nis_max=NIS_MAX[3], out=True)
+        nis_b, st_b = np.zeros(N, np.float32), np.zeros(N, np.uint8)
+        for k in range(32):
+            sl = slice(k, N, 32)
+            nis_b[sl], st_b[sl] = b.correct_pose(*(v[sl] for v in fx), r=fix_ref.R_FIX, nis_max=NIS_MAX[3], out=True)
+        _same(_snapshot(a), _snapshot(b), "count == N against 32 strided calls")
+    assert np.array_equal(_bits(nis_a), _bits(nis_b)) and np.array_equal(st_a, st_b)
+    assert np.all(st_a == ACC)
+
+
+def test_host_list_past_the_pinned_slot():
+    """a host list of more than 1 MiB (70 001 fixes) is staged with a copy instead of the pinned
+    slot, and its outputs come back through device scratch: same bits as the device list"""
+    import torch
+    n = 70001
+    rng = np.random.default_rng(n)
+    robot = np.arange(n, dtype=np.uint32)
+    x, y, th = (rng.normal(0, s, n).astype(np.float32) for s in (0.5, 0.5, 0.05))
+    x[::7] += np.float32(9.0)   # rejected at 16.27 against P00 = 1
+    with _engine("kf6", n) as a, _engine("kf6", n) as b:
+        nis_a, st_a = a.correct_pose(robot, x, y, th, r=fix_ref.R_FIX, nis_max=NIS_MAX[3], out=True)
+        rec = torch.from_numpy(fmskf.pose_fix_records(robot, x, y, th).view(np.int32).reshape(-1, 4)).cuda()
+        nis_b, st_b = b.correct_pose(fixes=rec, heading=True, r=fix_ref.R_FIX, nis_max=NIS_MAX[3], out=True)
+        _same(_snapshot(a), _snapshot(b), "host list > 1 MiB against the device list")
+    assert np.array_equal(_bits(nis_a), _bits(nis_b.cpu().numpy())) and np.array_equal(st_a, st_b.cpu().numpy())
+    assert np.all(st_a[::7] == REJ) and np.count_nonzero(st_a == ACC) > n // 2
+
+
+# ---------------------------------------------------------------------------- 5
+def test_edges_empty_and_single(orc):
+    """count == 0 is a no-op (NULL list, host and device); count == 1 works, for the last robot"""
+    import torch
+    e, tr = _warmed(orc, "kf6")
+    with e:
+        s0 = _snapshot(e)
+        L, prm = fmskf.load(), fmskf._lib.PoseFixParams()
+        prm.r[0] = prm.r[2] = prm.r[5] = 1e-4
+        prm.nis_max = float("inf")
+        for mem in (fmskf.MEM_HOST, fmskf.MEM_DEVICE):
+            assert L.fmskf_correct_pose(e.h, None, 0, prm, None, None, mem) == 0
+        out = e.correct_pose(np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, np.float32), out=True)
+        assert out[0].size == 0
+        e.correct_pose(fixes=torch.zeros((0, 4), dtype=torch.int32, device="cuda"))
+        _same(s0, _snapshot(e), "count == 0")
+        one = _fixes_for(tr, np.array([N - 1], np.uint32))
+        nis, st = e.correct_pose(*one, r=fix_ref.R_FIX, out=True)
+        assert st[0] == ACC and nis[0] > 0
+        s1 = _snapshot(e)
+        _same(s0, s1, "count == 1: the others", np.arange(N - 1))
+        x0, P0 = _f64_state(s0, "kf6")
+        xr, Pr, nr, _ = fix_ref.fix_update_f64(x0[-1:], P0[-1:], np.array([[float(v[0]) for v in one[1:]]]), 3, np.inf)
+        xg, Pg = _f64_state(s1, "kf6")
+        tol = MEASURED["kf6"]["3"]
+        assert np.abs(xg[-1] - xr[0]).max() <= 10 * tol["x"] and np.abs(Pg[-1] - Pr[0]).max() <= 10 * tol["P"]
+        assert e.get_counters()[3] == 0
+
+
+@pytest.mark.parametrize("key", ["kf6", "ekf9"])
+def test_edges_malformed_lists(orc, key):
+    """a device list with robot >= N, an adjacent duplicate and a descending neighbour: those
+    entries are FMSKF_FIX_IGNORED with NIS 0, counted in counter [3], their robots untouched (unless
+    listed well formed elsewhere), and the other entries are applied as if listed alone; the same
+    list from host memory is FMSKF_EINVAL with nothing changed"""
+    import torch
+    tr, tk = _warm(orc, key)
+    # 70 twice (the second ignored), 100 below its predecessor (ignored; 2049 after it is above 100), two >= N
+    robot = np.array([3, 70, 70, 2048, 100, 2049, N, 0xFFFFFFFF], np.uint32)
+    want = np.array([ACC, ACC, IGN, ACC, IGN, ACC, IGN, IGN], np.uint8)
+    rng = np.random.default_rng(5)
+    idx = np.minimum(robot.astype(np.int64), N - 1)
+    x = (tr.px[WARM - 1, idx] + rng.normal(0, 0.05, idx.size)).astype(np.float32)
+    y = (tr.py[WARM - 1, idx] + rng.normal(0, 0.05, idx.size)).astype(np.float32)
+    th = tr.th[WARM, idx].astype(np.float32)
+    good = want == ACC
+    with _engine(key) as a, _engine(key) as b:
+        for t in range(WARM):
+            a.tick(**tk[t])
+            b.tick(**tk[t])
+        s0 = _snapshot(a)
+        with pytest.raises(fmskf.FmskfError) as ei:
+            a.correct_pose(robot, x, y, th, r=fix_ref.R_FIX)
+        assert ei.value.code == fmskf._lib.EINVAL
+        _same(s0, _snapshot(a), "host list refused")
+        assert a.get_counters()[3] == 0
+        rec = torch.from_numpy(fmskf.pose_fix_records(robot, x, y, th).view(np.int32).reshape(-1, 4)).cuda()
+        nis, st = a.correct_pose(fixes=rec, heading=True, r=fix_ref.R_FIX, out=True)
+        nis, st = nis.cpu().numpy(), st.cpu().numpy()
+        assert np.array_equal(st, want)
+        assert np.all(nis[~good] == 0) and np.all(nis[good] > 0)
+        assert a.get_counters()[3] == 4
+        nis_b, st_b = b.correct_pose(robot[good], x[good], y[good], th[good], r=fix_ref.R_FIX, out=True)
+        assert np.array_equal(_bits(nis[good]), _bits(nis_b)) and np.all(st_b == ACC)
+        sa = _snapshot(a)
+        _same(sa, _snapshot(b), "the well-formed entries alone")
+        _same(s0, sa, "robots of ignored entries", np.setdiff1d(np.arange(N), robot[good].astype(np.int64)))
+        a.correct_pose(fixes=rec, heading=True, r=fix_ref.R_FIX)
+        assert a.get_counters()[3] == 8
+        a.reset()
+        assert a.get_counters()[3] == 0
+
+
+def test_edges_nan_and_bad_parameters(orc):
+    """a NaN coordinate is rejected and the state stays finite; bad parameters are FMSKF_EINVAL"""
+    e, tr = _warmed(orc, "kf6")
+    with e:
+        robot = _list129()[:16]
+        fx = _fixes_for(tr, robot)
+        x = fx[1].copy()
+        x[3] = np.nan
+        th = fx[3].copy()
+        th[5] = np.nan
+        s0 = _snapshot(e)
+        nis, st = e.correct_pose(fx[0], x, fx[2], th, r=fix_ref.R_FIX, out=True)
+        assert st[3] == REJ and st[5] == REJ and np.isnan(nis[3]) and np.isnan(nis[5])
+        assert np.all(np.delete(st, [3, 5]) == ACC)
+        s1 = _snapshot(e)
+        assert all(np.all(np.isfinite(v)) for v in s1[:2]) and e.get_counters()[0] == 0
+        _same(s0, s1, "NaN fixes", robot[[3, 5]].astype(np.int64))
+        nis, st = e.correct_pose(fx[0], x, fx[2], th, r=fix_ref.R_FIX, out=True, heading=False)
+        assert st[3] == REJ and st[5] == ACC   # theta is not read without FMSKF_FIX_HEADING
+        s2 = _snapshot(e)
+        inf = float("inf")
+        for bad in (dict(r=[1e-4, 0, 0.0, 0, 0, 1e-4]), dict(r=[1e-4, 0, -1e-4, 0, 0, 1e-4]),
+                    dict(r=[1e-4, np.nan, 1e-4, 0, 0, 1e-4]), dict(r=[1e-4, 0, 1e-4, 0, 0, 0.0]),
+                    dict(r=[inf, 0, 1e-4, 0, 0, 1e-4]), dict(nis_max=float("nan")), dict(nis_max=0.0),
+                    dict(nis_max=-1.0)):
+            with pytest.raises(fmskf.FmskfError) as ei:
+                e.correct_pose(*fx, **{"r": fix_ref.R_FIX, **bad})
+            assert ei.value.code == fmskf._lib.EINVAL, bad
+        # without the heading only the 2 x 2 block of R is read
+        e.correct_pose(fx[0], fx[1], fx[2], r=[1e-4, 0, 1e-4, np.nan, np.nan, -1.0])
+        L, prm = fmskf.load(), fmskf._lib.PoseFixParams()
+        prm.r[0] = prm.r[2] = prm.r[5] = 1e-4
+        prm.nis_max = inf
+        rec = fmskf.pose_fix_records(*fx)
+        p = rec.ctypes.data
+        s3 = _snapshot(e)
+        prm.flags = 2
+        assert L.fmskf_correct_pose(e.h, p, rec.size, prm, None, None, fmskf.MEM_HOST) == fmskf._lib.EINVAL
+        prm.flags = 1
+        assert L.fmskf_correct_pose(e.h, p, rec.size, None, None, None, fmskf.MEM_HOST) == fmskf._lib.EINVAL
+        assert L.fmskf_correct_pose(e.h, None, rec.size, prm, None, None, fmskf.MEM_HOST) == fmskf._lib.EINVAL
+        assert L.fmskf_correct_pose(e.h, p, rec.size, prm, None, None, 7) == fmskf._lib.EINVAL
+        assert L.fmskf_correct_pose(e.h, p, N + 1, prm, None, None, fmskf.MEM_DEVICE) == fmskf._lib.EINVAL
+        _same(s3, _snapshot(e), "refused calls")
+        assert not np.array_equal(_bits(s2[1]), _bits(s3[1]))
+
+
+@pytest.mark.parametrize("model,flags", [("rs", 0), ("kf12d", 0), ("ekf9", fmskf.CFG_COMP_POS)])
+def test_edges_unsupported_models(model, flags):
+    with Engine(model, 300, flags=flags) as e:
+        with pytest.raises(fmskf.FmskfError) as ei:
+            e.correct_pose(np.array([1], np.uint32), np.zeros(1, np.float32), np.zeros(1, np.float32))
+        assert ei.value.code == fmskf._lib.ENOTSUP
+        with pytest.raises(fmskf.FmskfError) as ei:  # whatever the count
+            e.correct_pose(np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, np.float32))
+        assert ei.value.code == fmskf._lib.ENOTSUP
+
+
+# ---------------------------------------------------------------------------- 6
+def test_checkpoint_of_a_handle_without_fixes(orc, tmp_path):
+    """a handle that never fuses a fix writes the checkpoint it always wrote: byte-identical to
+    that of a second handle on the same run whose only pose-fix calls change nothing (an empty
+    list, a refused host list), and a handle that did fuse fixes differs from both only through
+    its state (the file has the same length: the call adds no section)"""
+    tr, tk = _warm(orc, "kf6")
+    robot = _list129()
+    fx = _fixes_for(tr, robot)
+    files = []
+    for mode in ("never", "noop", "fused"):
+        with _engine("kf6") as e:
+            for t in range(WARM):
+                e.tick(**tk[t])
+                if mode == "noop" and t == 20:
+                    e.correct_pose(robot[:0], fx[1][:0], fx[2][:0])
+                    with pytest.raises(fmskf.FmskfError):
+                        e.correct_pose(robot[::-1].copy(), fx[1], fx[2])
+                if mode == "fused" and t == 20:
+                    e.correct_pose(*fx, r=fix_ref.R_FIX)
+            p = tmp_path / f"{mode}.ckpt"
+            e.save_state(p)
+            files.append(p.read_bytes())
+    assert files[0] == files[1]
+    assert len(files[2]) == len(files[0]) and files[2] != files[0]
+
+
+def test_persistent_gate_is_not_touched(orc):
+    """a handle with a persistent gate (fmskf_set_gate) has the same gate state before and after
+    a pose-fix call, and the call's own nis_max is what decides"""
+    e, tr = _warmed(orc, "kf6")
+    with e:
+        e.set_gate(18.47, 3)
+        e.tick(**_warm(orc, "kf6")[1][WARM])
+        g0 = e.get_gate()
+        robot = _list129()
+        fx = _fixes_for(tr, robot, sigma=0.01)
+        e.correct_pose(*fx, r=fix_ref.R_FIX)
+        _, st = e.correct_pose(fx[0], fx[1] + np.float32(5.0), fx[2], fx[3], r=fix_ref.R_FIX, nis_max=13.82, out=True)
+        assert np.all(st == REJ)
+        g1 = e.get_gate()
+        for k in g0:
+            assert np.array_equal(_bits(g0[k]), _bits(g1[k])), k
+
+
+# ---------------------------------------------------------------------------- 7
+@pytest.mark.parametrize("key,n", [("kf6", 51_200_003), ("ekf9", 23_900_001)])
+def test_arrays_past_4_gib(key, n):
+    """Past 4 GiB of packed P (KF6 beyond 51.1 M robots, EKF9 beyond 23.8 M) a 32-bit lane offset
+    cannot reach every row: the kernel's 64-bit addressing form.  On a fresh fleet every robot
+    holds the same state, so the listed robots -- the first, the last, the tile edges, the ones on
+    either side of the 4 GiB offset -- must come out bit for bit as robots 0..128 of a small fleet
+    given the same fixes: pose after the first call, NIS (which reads x and P) of a second call;
+    and every robot that is not listed still has the reset pose."""
+    rows = 21 if key == "kf6" else 45
+    edge = (1 << 32) // (rows * 4 * 2048) * 2048   # the first robot of the tile that crosses 4 GiB of P
+    rng = np.random.default_rng(n)
+    must = np.array([0, 2047, 2048, edge - 1, edge, edge + 2047, edge + 2048, n - 2, n - 1])
+    robot = np.unique(np.concatenate([must, rng.choice(n, 120, replace=False)])).astype(np.uint32)
+    c = robot.size
+    x = rng.normal(0, 0.3, c).astype(np.float32)
+    y = rng.normal(0, 0.3, c).astype(np.float32)
+    th = rng.normal(0, 0.03, c).astype(np.float32)
+    small = np.arange(c, dtype=np.uint32)
+    with _engine(key, 4113) as s:
+        s.correct_pose(small, x, y, th, r=fix_ref.R_FIX)
+        pose_s = s.get_pose()[:, :c]
+        nis_s, st_s = s.correct_pose(small, x + np.float32(0.01), y, th, r=fix_ref.R_FIX, nis_max=NIS_MAX[3], out=True)
+    with _engine(key, n) as e:
+        assert rows * e.cfg.n_instances * 4 > 0xFFFFFFFF
+        e.correct_pose(robot, x, y, th, r=fix_ref.R_FIX)
+        pose = e.get_pose()
+        nis, st = e.correct_pose(robot, x + np.float32(0.01), y, th, r=fix_ref.R_FIX, nis_max=NIS_MAX[3], out=True)
+        assert e.get_counters()[0] == 0 and e.get_counters()[3] == 0
+    assert np.array_equal(_bits(pose[:, robot]), _bits(pose_s))
+    assert np.array_equal(_bits(nis), _bits(nis_s)) and np.array_equal(st, st_s)
+    assert np.count_nonzero(pose.any(axis=0)) == c and np.all(pose[:, robot].any(axis=0))

@@ -44,6 +44,10 @@ def main():
                          "wrap, which the gate rejects)")
     ap.add_argument("--ktime", action="store_true",
                     help="--op tick: a second timed loop with per-launch kernel events (fmskf_set_timing)")
+    ap.add_argument("--pose-fix", type=float, default=None, metavar="DENSITY",
+                    help="KF6 / EKF9: time the absolute pose-fix pass (fmskf_correct_pose) alone, by kernel time as "
+                         "--ktime does, with this share of the robots listed (1: every robot, 0.03125: one in 32)")
+    ap.add_argument("--fix-m", type=int, choices=[2, 3], default=3, help="--pose-fix: 3 = with the heading")
     ap.add_argument("--comm", action="store_true",
                     help="--op ens_async: a world-1 RCCL communicator on the handle (fmskf_comm_init)")
     args = ap.parse_args()
@@ -108,6 +112,8 @@ def main():
                dict(yaw_deg=yaw[r], gyro_z_dps=gz[r], rpm=rpm[r]) if args.model == "kf6" else
                dict(raw=raw[r]) if args.model == "ekf9" else dict(z=z[r]) for r in range(R)]
         preps = [e.prepare(valid=vm[r], **kws[r]) for r in range(R)]
+    if args.pose_fix is not None:
+        return bench_pose_fix(args, e, n, preps, dev)
     if args.host:
         return bench_host(args, e, n, yaw, gz, rpm)
     if args.op in ("pipeline", "pipeline_graph", "isr", "isr_graph", "isr_can", "can_isr", "isr_can_graph",
@@ -265,6 +271,57 @@ def main():
                       "steps_per_s": n / (ms_tick * 1e-3),
                       "algo_GBps": BYTES[args.model] * n / (ms_tick * 1e-3) / 1e9, "finite": ok, **extra}),
           flush=True)
+
+
+def bench_pose_fix(args, e, n, preps, dev):
+    """The pose-fix pass alone at a given density (robots 0, s, 2 s, ... with s = round(1 / density)),
+    kernel time per launch (fmskf_set_timing): back to back, and each pass right behind a tick (the
+    state as a tick leaves it in the caches), with the tick's own kernel time from the same run."""
+    import numpy as np
+    import torch
+    import fmskf
+    R = len(preps)
+    for k in range(20):
+        e.tick_prepared(preps[k % R])
+    stride = max(1, int(round(1.0 / args.pose_fix)))
+    robot = np.arange(0, n, stride, dtype=np.uint32)
+    pose = e.get_pose()[:, robot]
+    rng = np.random.default_rng(1)
+    nz = rng.normal(0.0, 1e-2, (3, robot.size)).astype(np.float32)
+    rec = fmskf.pose_fix_records(robot, pose[0] + nz[0], pose[1] + nz[1], pose[2] + nz[2])
+    rec = torch.from_numpy(rec.view(np.int32).reshape(-1, 4)).to(dev)
+    kw = dict(fixes=rec, heading=args.fix_m == 3, r=1e-4)
+    for _ in range(5):
+        e.correct_pose(**kw)
+    e.set_timing(True)
+    for _ in range(args.ticks):
+        e.correct_pose(**kw)
+    tot, cnt = e.kernel_time_total()
+    back_to_back = tot * 1e3 / max(cnt, 1)
+    tick_ms = fix_ms = 0.0
+    for k in range(args.ticks):
+        e.set_timing(True)
+        e.tick_prepared(preps[(20 + k) % R])
+        tick_ms += e.kernel_time_total()[0]
+        e.set_timing(True)
+        e.correct_pose(**kw)
+        fix_ms += e.kernel_time_total()[0]
+    e.set_timing(False)
+    comp = 5 if args.comp else 0
+    rows = {"kf6": 27 + comp, "ekf9": 54 + 1}[args.model]
+    # line traffic: a wave's 64 fixes touch 64 * 4 * stride bytes of each row, in 128-byte lines,
+    # read and written; plus the 16-byte fix
+    lines_per_fix_row = min(1.0, stride / 32.0)
+    x, P = e.get_state()
+    print(json.dumps({"model": args.model, "n": n, "op": "pose_fix", "comp": args.comp, "m": args.fix_m,
+                      "density": 1.0 / stride, "count": int(robot.size),
+                      "fix_kernel_us": back_to_back, "fix_kernel_us_after_tick": fix_ms * 1e3 / args.ticks,
+                      "tick_kernel_us": tick_ms * 1e3 / args.ticks,
+                      "state_bytes_per_fix": rows * 4 * 2 + 16,
+                      "line_bytes_per_fix_est": rows * 128 * 2 * lines_per_fix_row + 16,
+                      "line_MB_per_pass_est": robot.size * (rows * 128 * 2 * lines_per_fix_row + 16) / 1e6,
+                      "ignored": e.get_counters()[3],
+                      "finite": bool(np.isfinite(x).all() and np.isfinite(P).all())}), flush=True)
 
 
 def bench_host(args, e, n, yaw, gz, rpm):
