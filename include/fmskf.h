@@ -559,7 +559,9 @@ int fmskf_export_vehicle_info(fmskf_handle h, fmskf_vehicle_info *out, const uin
  * graph, then replay it: one launch per tick for launch-bound (small-N) fleets.  Only
  * device-pointer calls (FMSKF_MEM_DEVICE, or NULL planes reading the device state) can be
  * captured; a call that needs a host round trip fails during capture.  A new begin
- * replaces the previous graph. */
+ * replaces the previous graph.  A replay starts from the handle's current state, whatever
+ * direct calls came since the capture: the results are those of the captured calls made
+ * directly at that point (with the control parameters of the capture). */
 int fmskf_graph_begin(fmskf_handle h);
 int fmskf_graph_end(fmskf_handle h);
 int fmskf_graph_launch(fmskf_handle h, uint32_t times);

@@ -182,7 +182,9 @@ struct fmskf_ctx {
   // they equal the motor state's sums (the last predict read those, and nothing changed them
   // since); rs_prev_stale: the prev planes are behind, the fused RS CAN ISR took the previous sums
   // from the motor state and wrote no prev (k_isr_rs PS).  stale implies synced.  Every reader of
-  // the prev planes and every writer of the motor sums calls rs_prev_materialize first.
+  // the prev planes and every writer of the motor sums calls rs_prev_materialize first; a graph
+  // replay (fmskf_graph_launch) is such a reader and writer, whatever it captured: captured RS
+  // ticks never take the PS form, and the host cannot follow what the replayed calls do.
   bool rs_prev_synced = false, rs_prev_stale = false;
   // The control step's outputs nothing reads back (vel_tgt, FF_PI_D now_tgt / now_ctrl) are
   // formed on demand (round 6, ctrl_lane.hpp ctrl_derive_lane): ctrl_derived_stale says the last
@@ -190,6 +192,8 @@ struct fmskf_ctx {
   // checkpoint form them first (ctrl_materialize), and so does fmskf_set_power, since the forming
   // reads the power flags the step ran with.  Inside a graph capture the step stores them itself
   // (the host cannot follow the replays): graph_has_ctrl marks a captured sequence with a step.
+  // fmskf_graph_launch forms them before it replays, like fmskf_graph_begin before it captures:
+  // the replayed calls may change the power flags (a captured fmskf_set_power).
   bool ctrl_derived_stale = false, graph_has_ctrl = false;
   // the motor history order (DevState::m_par) at the start and the end of the captured sequence
   uint32_t graph_par0 = 0, graph_par_end = 0;

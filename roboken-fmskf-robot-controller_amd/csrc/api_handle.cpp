@@ -636,6 +636,12 @@ int fmskf_graph_launch(fmskf_handle h, uint32_t times) {
     if (!h->graph_exec) fail(FMSKF_EINVAL, "no graph captured");
     if (h->capturing) fail(FMSKF_EINVAL, "capture still open");
     DeviceGuard g(h->cfg.device);
+    // the replay is a reader like any direct call: direct calls made since the capture may have
+    // left the prev planes behind (a PS tick) or the control outputs to be formed.  Captured RS
+    // ticks read and write the prev planes (so no stale flag may outlive the replay and overwrite
+    // what they wrote), and a captured fmskf_set_power changes the flags the forming reads
+    rs_prev_materialize(h);
+    ctrl_materialize(h);
     for (uint32_t k = 0; k < times; k++) {
       if (h->s.m_par != h->graph_par0) {  // replays start from the capture's motor history order
         launch_check(launch_motor_swap(h->s, h->stream), "motor history order");

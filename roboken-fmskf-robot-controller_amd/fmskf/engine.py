@@ -551,9 +551,16 @@ class Engine:
         check(load().fmskf_set_ctrl_params(self.h, C.byref(p)), "set_ctrl_params")
 
     def set_power(self, on=None):
+        """on: None (all on), a scalar or [N] host array, or an [N] uint8 device tensor (a call
+        that is captured)"""
         a = _Args()
-        p = a.ptr(None if on is None else np.broadcast_to(np.asarray(on, np.uint8), (self.n,)),
-                  np.uint8)
+        if on is not None and _is_torch(on) and on.is_cuda:
+            if str(on.dtype) != "torch.uint8" or on.numel() < self.n:
+                raise TypeError(f"on: want an [N] uint8 device tensor, got {on.dtype} x {on.numel()}")
+            p = a.ptr(on)
+        else:
+            p = a.ptr(None if on is None else np.broadcast_to(np.asarray(on, np.uint8), (self.n,)),
+                      np.uint8)
         check(load().fmskf_set_power(self.h, p, MEM_HOST if a.mem is None else a.mem), "set_power")
 
     def set_target_vel(self, vel, acl, jrk, mask=None):

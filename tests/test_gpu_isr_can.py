@@ -155,7 +155,8 @@ def test_isr_tick_can_kf12d_counts_three_kernels():
 # odometry's previous sums live (fmskf_ctx rs_prev_synced / rs_prev_stale)
 RS_OPS = (["fused"] * 3 + ["prev"] + ["split"] + ["fused"] * 2 + ["caller_sums"] + ["fused"] * 2 + ["ckpt"]
           + ["fused"] * 2 + ["graph"] + ["fused"] + ["predict_only"] + ["fused"] * 2 + ["prev", "fused", "reset"]
-          + ["fused"] * 3 + ["ingest_only", "fused", "fused", "prev"])
+          + ["fused"] * 3 + ["ingest_only", "fused", "fused", "prev"]
+          + ["graph_late", "prev", "fused", "prev"])
 
 
 def test_rs_prev_in_motor_sums(orc, tmp_path):
@@ -168,7 +169,7 @@ def test_rs_prev_in_motor_sums(orc, tmp_path):
     36-51): the pose after every step and the previous sums at the `prev` steps, bit for bit."""
     import torch
     n = 1001
-    T = len(RS_OPS) + 2
+    T = len(RS_OPS) + 2 + 4  # `graph` reads one tick more than the other steps, `graph_late` three
     tr = Trajectory(n, T, seed=77)
     yaw = tr.kf6_inputs()[0]
     csum = tr.rs_inputs()[1]  # [T][4][N] sums unrelated to the motor state's
@@ -240,6 +241,27 @@ def test_rs_prev_in_motor_sums(orc, tmp_path):
                     mb.rx(f2, s2)
                     oracle_tick(t + k)
                 t += 1
+            elif op == "graph_late":  # two direct fused ticks between graph_end and the replays:
+                # the second runs PS and leaves the prev planes a frame behind the captured kernel
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a))  # noqa: E731
+                fd, sd, yd = up(f).cuda(), up(s).cuda(), up(yaw[t]).cuda()
+                e.graph_begin()
+                e.isr_tick_can(fd, sd, frames=False, yaw_deg=yd)
+                e.graph_end()
+                for k in range(4):
+                    f2, s2 = tr.can_frames(t + k)
+                    if k < 2:
+                        e.isr_tick_can(f2, s2, frames=False, yaw_deg=yaw[t + k])
+                    else:
+                        fd.copy_(up(f2))
+                        sd.copy_(up(s2))
+                        yd.copy_(up(yaw[t + k]))
+                        e.graph_launch(1)
+                    mb.rx(f2, s2)
+                    oracle_tick(t + k)
+                    x, _ = e.get_state()
+                    np.testing.assert_array_equal(bits(x[:3]), bits(pos), err_msg=f"pose in graph_late at tick {t + k}")
+                t += 3
             elif op == "reset":
                 e.reset()
                 mb = orc.MotorBatch(n)
