@@ -253,6 +253,81 @@ int fmskf_set_gate(fmskf_handle h, const fmskf_gate *g);   /* NULL = gate off (t
 /* all [N]; any pointer may be NULL */
 int fmskf_get_gate(fmskf_handle h, float *nis, uint8_t *status, uint8_t *run, uint32_t *rejects, uint32_t mem);
 
+/* ---- per-row innovation gate (EKF9) ------------------------------------------- */
+/* Off by default: a handle that never sets a row gate runs the kernels and computes the bits it
+ * always did, and writes the checkpoints it always wrote.
+ *
+ * With the default diagonal R the EKF9 measurement update is six scalar updates in sequence, in
+ * the row order heading, gyro z, ax, ay, vbx, vby, each on the state the previous one left.  The
+ * row gate decides each scalar row on its own normalised innovation, so one slipping wheel drops
+ * the two wheel rows and keeps the IMU rows, and one heading glitch drops the heading row alone.
+ *
+ * With a row gate set, every EKF9 measurement update -- fmskf_tick, fmskf_correct, each tick of
+ * fmskf_tick_many, with or without a `valid` mask -- is that loop over a = 0..5 on the
+ * innovation y (the heading component against the compensated heading and wrapped to [-pi, pi),
+ * as ever).  At row a, hp = H_a P, s = H_a hp + R[a][a], si = 1 / s and g = y[a] * si are formed
+ * exactly as in the ungated update; then, with run[a] the row's count of consecutive rejections,
+ *     d2     = y[a] * g                       (one rounded product: y[a]^2 / s)
+ *     forced = max_consecutive > 0 && run[a] >= max_consecutive
+ *     apply  = forced || d2 <= d2_max[a]      (a NaN d2 is rejected unless forced)
+ * An applied row runs exactly the operations of the ungated loop: x += hp g (the heading through
+ * its compensated sum), the later innovations y[b] -= (H_b hp) g, P -= (hp si) hp^T.  A rejected
+ * row touches nothing: not x, not the heading's low part, not P, not the later y[b].  The
+ * heading's renormalisation after the loop and the predict run as ever.  So
+ *   - an update in which every row is applied equals the ungated update bit for bit;
+ *   - an update in which every row is rejected equals the valid == 0 skip;
+ *   - any other pattern equals the ungated sequential update with R[a][a] = +INFINITY on the
+ *     rejected rows, value for value (1 / inf = 0 makes every term of such a row an exact zero);
+ *     only the sign of a zero may differ.
+ *
+ * Per-robot, per-row gate state (fmskf_get_row_gate; planes [FMSKF_EKF9_ROWS][N], row-major):
+ *   status  FMSKF_GATE_* of the last updating call: NONE in every row when it carried no
+ *           measurement for the robot (valid == 0) or none ran yet; FORCED whenever `forced`
+ *           held, whatever d2; else ACCEPTED or REJECTED
+ *   run     0 after an applied row, +1 after a rejected one, saturating at 255; unchanged by a
+ *           call without a measurement
+ *   d2      the last evaluated value (applied or not), kept only with FMSKF_ROW_GATE_D2;
+ *           unchanged when the robot had no measurement; 0 before the first
+ * fmskf_tick_many leaves the last tick's status and the last evaluated d2.
+ *
+ * All six d2_max = +INFINITY with max_consecutive = 0 is monitor-only: nothing is rejected, the
+ * state equals an ungated handle's bit for bit, and d2 is reported.
+ *
+ * EKF9 without FMSKF_CFG_COMP_POS and with a diagonal R (the sequential form) only:
+ * fmskf_set_row_gate returns FMSKF_ENOTSUP for RS, KF6, KF12D, EKF9 with FMSKF_CFG_COMP_POS and
+ * an EKF9 handle whose R has an off-diagonal term; FMSKF_EINVAL for a d2_max entry that is NaN
+ * or <= 0, for max_consecutive > 255, for unknown flag bits, and inside a graph capture.
+ * Setting a gate on a handle that has none starts from a zero gate state; changing the thresholds
+ * or flags of a set gate keeps the state; NULL turns it off.  fmskf_get_row_gate returns
+ * FMSKF_EINVAL while no row gate is set, and when d2 is asked for and the gate was set without
+ * FMSKF_ROW_GATE_D2.
+ *
+ * fmskf_reset zeroes the gate state and keeps the configuration; fmskf_set_state leaves the gate
+ * state alone; fmskf_save_state writes it as an optional section group (the words, then the d2
+ * planes; the last group of the body) only while a row gate is set, so every other handle's file
+ * is byte for byte what it was; fmskf_load_state restores the group into a row-gated handle,
+ * zeroes the gate state when the file has none, and ignores the file's group when the handle has
+ * no row gate.  fmskf_set_gate (KF6) and fmskf_correct_pose are untouched by and independent of
+ * the row gate.
+ *
+ * The fused forms have no row-gated counterpart and take the fallbacks the KF6 gate takes: with a
+ * row gate set fmskf_isr_tick / fmskf_isr_tick_can run the CAN RX kernel (where it applies), the
+ * gated tick, the control step and the frame (counters [1] and [2] count them), and
+ * fmskf_tick_ensemble / fmskf_tick_ensemble_begin tick gated, then run the stand-alone record.
+ * All of them can be captured (fmskf_graph_begin) like the plain tick.  A row-gated tick moves
+ * 472 B per robot instead of 456 (the gate word read and written), 496 B with the d2 planes. */
+#define FMSKF_EKF9_ROWS 6          /* heading, gyro z, ax, ay, vbx, vby: the order of the update */
+#define FMSKF_ROW_GATE_D2 1u       /* keep every row's last evaluated d2 (+24 B stored per robot-tick) */
+typedef struct fmskf_row_gate {
+  float d2_max[FMSKF_EKF9_ROWS];   /* row a is rejected when !(d2[a] <= d2_max[a]); +INFINITY: never */
+  uint32_t max_consecutive;        /* 0 = never force; else a row rejected this many times in a row is
+                                      applied whatever its d2 (per row; runs saturate at 255) */
+  uint32_t flags;                  /* FMSKF_ROW_GATE_* */
+} fmskf_row_gate;
+int fmskf_set_row_gate(fmskf_handle h, const fmskf_row_gate *g);   /* NULL = off (the default) */
+/* status [6][N] (FMSKF_GATE_NONE / ACCEPTED / REJECTED / FORCED), run [6][N], d2 [6][N]; any may be NULL */
+int fmskf_get_row_gate(fmskf_handle h, uint8_t *status, uint8_t *run, float *d2, uint32_t mem);
+
 /* ---- absolute pose fixes (KF6, EKF9) ------------------------------------------ */
 /* The tick's measurements are heading, yaw rate and wheel velocity: px and py are open-loop
  * integrals and their covariance only grows.  fmskf_correct_pose fuses low-rate absolute fixes

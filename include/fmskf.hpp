@@ -96,6 +96,14 @@ class Robots {
     check(fmskf_get_gate(h_, nis, status, run, rejects, mem), "fmskf_get_gate");
   }
 
+  // the per-row innovation gate of an EKF9 fleet (fmskf_set_row_gate; NULL = off) and its
+  // per-robot, per-row readout ([FMSKF_EKF9_ROWS][N] each, any pointer may be NULL): FMSKF_GATE_*
+  // status, consecutive rejections and, with FMSKF_ROW_GATE_D2, the last d2
+  void set_row_gate(const fmskf_row_gate *g) { check(fmskf_set_row_gate(h_, g), "fmskf_set_row_gate"); }
+  void get_row_gate(uint8_t *status, uint8_t *run, float *d2, uint32_t mem = FMSKF_MEM_HOST) {
+    check(fmskf_get_row_gate(h_, status, run, d2, mem), "fmskf_get_row_gate");
+  }
+
   // absolute pose fixes of a sorted subset of the robots (fmskf_correct_pose: a camera / UWB /
   // landmark callback, between two ISRs): nis / status [count] receive the evaluated NIS and
   // FMSKF_GATE_ACCEPTED / _REJECTED / FMSKF_FIX_IGNORED, either may be NULL

@@ -12,7 +12,10 @@ namespace {
 // counters), 2 IMU ingest, 4 motor ingest, 8 control (state + parameters), 16 the innovation
 // gate's per-robot state (fmskf_set_gate: the gate words, the NIS plane; written only while a gate
 // is set, so a gate-less handle's file is what it always was; the last group of the body, so a
-// handle without a gate loads such a file by not reading it).
+// handle without a gate loads such a file by not reading it), 32 the EKF9 row gate's per-robot
+// state (fmskf_set_row_gate: the words, then the six d2 planes packed to [6][N]; written only while
+// a row gate is set and the last group of the body, like the KF6 gate's, which it never meets: the
+// two gates belong to different models).
 // Format 2 ('FMSKFCK2'): the header records every layout choice a section's bytes depend on
 // (estimator pitch / tile / element size, the motor sums' pitch, the control arrays' tiling
 // and pitch) and a checksum of everything after the header; a file whose layout differs from
@@ -47,10 +50,20 @@ struct CkHeader {
   uint32_t layout;
 };
 constexpr uint32_t kCkPrevRows = 1u, kCkSumSplit = 2u, kCkImuYg = 4u, kCkRpmPrev = 8u, kCkImuRow = 16u;
+// rows > 1: `rows` device rows `pitch` bytes apart, packed in the file (bytes in all)
 struct CkSection {
   void *dev;
   size_t bytes;
+  size_t rows = 1, pitch = 0;
 };
+// the device address and length of the run of a section's packed bytes that starts at `off`:
+// to the end of its row, kCkChunk at the most
+constexpr size_t kCkChunk = (size_t)64 << 20;  // host staging per copy: 64 MiB, a word multiple
+char *ck_run(const CkSection &c, size_t off, size_t *len) {
+  const size_t rb = c.bytes / c.rows, r = off / rb, o = off % rb;
+  *len = std::min(kCkChunk, rb - o);
+  return (char *)c.dev + r * c.pitch + o;
+}
 std::vector<CkSection> ck_sections(fmskf_ctx *h, uint32_t groups) {
   DevState &s = h->s;
   const uint64_t n = s.n, pp = s.pitch;
@@ -97,6 +110,10 @@ std::vector<CkSection> ck_sections(fmskf_ctx *h, uint32_t groups) {
   if (groups & 16) {
     v.push_back({h->gate.word, (size_t)n * 4});
     v.push_back({h->gate.nis, (size_t)n * 4});
+  }
+  if (groups & 32) {
+    v.push_back({h->rowgate.word, (size_t)n * 8});
+    v.push_back({h->rowgate.d2, (size_t)FMSKF_EKF9_ROWS * n * 4, FMSKF_EKF9_ROWS, (size_t)h->rowgate.d2_pitch * 4});
   }
   return v;
 }
@@ -158,8 +175,6 @@ struct CkHash {
   }
 };
 
-constexpr size_t kCkChunk = (size_t)64 << 20;  // host staging per copy: 64 MiB, a word multiple
-
 struct File {
   FILE *f = nullptr;
   File(const char *path, const char *mode) : f(fopen(path, mode)) {
@@ -194,7 +209,7 @@ int fmskf_save_state(fmskf_handle h, const char *path) {
     memcpy(hd.magic, kCkMagic, 8);
     ck_layout(h, &hd);
     hd.groups = 1u | (h->s.imu_reg ? 2u : 0u) | (h->s.m_sum_lo ? 4u : 0u) | (h->ctrl_ready ? 8u : 0u) |
-                (h->gate_on ? 16u : 0u);
+                (h->gate_on ? 16u : 0u) | (h->rowgate_on ? 32u : 0u);
     rs_prev_materialize(h);  // the file holds the odometry's previous sums in the prev planes
     ctrl_materialize(h);     // and the control step's outputs
     // and the whole WT901 register file in its planes (no row-resident registers)
@@ -213,10 +228,10 @@ int fmskf_save_state(fmskf_handle h, const char *path) {
     for (const CkSection &c : ck_sections(h, hd.groups)) {
       const uint64_t b = c.bytes;
       put(&b, 8);
-      for (size_t off = 0; off < c.bytes; off += kCkChunk) {  // bounded host memory
-        const size_t len = std::min(kCkChunk, c.bytes - off);
+      for (size_t off = 0, len = 0; off < c.bytes; off += len) {  // bounded host memory
+        const char *src = ck_run(c, off, &len);
         buf.resize(len);
-        hip_check(hipMemcpy(buf.data(), (const char *)c.dev + off, len, hipMemcpyDeviceToHost), "save D2H");
+        hip_check(hipMemcpy(buf.data(), src, len, hipMemcpyDeviceToHost), "save D2H");
         put(buf.data(), len);
       }
     }
@@ -250,7 +265,7 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     CkHeader me{};
     ck_layout(h, &me);
     if (hd.abi != me.abi || hd.model != me.model || hd.n != me.n || hd.pitch != me.pitch ||
-        hd.tile != me.tile || hd.elem != me.elem || hd.flags != me.flags || (hd.groups & ~31u))
+        hd.tile != me.tile || hd.elem != me.elem || hd.flags != me.flags || (hd.groups & ~63u))
       fail(FMSKF_EINVAL, "checkpoint does not match this handle (ABI, model, flags, N or layout)");
     if ((hd.groups & 4) && hd.m_pitch != me.m_pitch) fail(FMSKF_EINVAL, "checkpoint motor layout differs");
     if (hd.layout != me.layout)
@@ -285,7 +300,9 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     if (hd.groups & 4) ensure_motors(h);
     if (hd.groups & 8) ensure_ctrl(h);
     // the gate group goes into a handle with a gate set; one without has no gate state to restore
-    const std::vector<CkSection> secs = ck_sections(h, h->gate_on ? hd.groups : hd.groups & ~16u);
+    // (nor has one without a row gate)
+    const std::vector<CkSection> secs =
+        ck_sections(h, hd.groups & ~(h->gate_on ? 0u : 16u) & ~(h->rowgate_on ? 0u : 32u));
     // the section sizes follow from the (validated) layout; check them against the file's
     // before any copy
     const long first = f.tell();
@@ -301,6 +318,7 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     if (!(hd.groups & 4) && h->s.m_sum_lo) zero_motors(h);
     if (!(hd.groups & 8) && h->ctrl_ready) zero_ctrl(h);
     if (!(hd.groups & 16)) zero_gate(h);
+    if (!(hd.groups & 32)) zero_rowgate(h);
     h->rs_prev_synced = h->rs_prev_stale = false;  // the prev planes come from the file
     h->ctrl_derived_stale = false;                  // and the control outputs
     hip_check(hipStreamSynchronize(h->stream), "load sync");
@@ -308,11 +326,11 @@ int fmskf_load_state(fmskf_handle h, const char *path) {
     for (const CkSection &c : secs) {
       uint64_t b = 0;
       f.read(&b, 8);
-      for (size_t off = 0; off < c.bytes; off += kCkChunk) {
-        const size_t len = std::min(kCkChunk, c.bytes - off);
+      for (size_t off = 0, len = 0; off < c.bytes; off += len) {
+        char *dst = ck_run(c, off, &len);
         buf.resize(len);
         f.read(buf.data(), len);
-        hip_check(hipMemcpy((char *)c.dev + off, buf.data(), len, hipMemcpyHostToDevice), "load H2D");
+        hip_check(hipMemcpy(dst, buf.data(), len, hipMemcpyHostToDevice), "load H2D");
       }
     }
     if (hd.groups & 8) h->cprm = cp;

@@ -61,8 +61,9 @@ void ensure_shift(fmskf_ctx *h) {
 
 // the models whose tick kernel writes the ensemble block records of the state it stores
 bool fused_record(const fmskf_ctx *h) {
-  // (a gated KF6 ticks through the gated kernels, then takes the stand-alone record)
-  return (h->cfg.model == FMSKF_MODEL_KF6 && !h->gate_on) || (h->cfg.model == FMSKF_MODEL_EKF9 && h->s.tile) ||
+  // (a gated KF6 and a row-gated EKF9 tick through the gated kernels, then take the stand-alone record)
+  return (h->cfg.model == FMSKF_MODEL_KF6 && !h->gate_on) ||
+         (h->cfg.model == FMSKF_MODEL_EKF9 && h->s.tile && !h->rowgate_on) ||
          (h->cfg.model == FMSKF_MODEL_KF12D && h->s.tile && h->kf12.decor);
 }
 

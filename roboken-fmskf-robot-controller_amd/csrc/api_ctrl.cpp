@@ -229,7 +229,7 @@ static void isr_launches(fmskf_ctx *h, const TickIn &t, uint8_t *dst) {
     if (!t.rec && !t.rpm) ensure_motors(h);
     fused = launch_isr_kf6(h->s, t, h->kf6, libm, h->ctrl, p, dst, h->stream);
     if (fused != (int)hipErrorNotSupported) launch_check(fused, "isr launch");
-  } else if (h->cfg.model == FMSKF_MODEL_EKF9 && isr_kf6_fused()) {
+  } else if (h->cfg.model == FMSKF_MODEL_EKF9 && isr_kf6_fused() && !h->rowgate_on) {  // (nor has a row-gated EKF9)
     if (!t.rpm) ensure_motors(h);
     fused = launch_isr_ekf9(h->s, t, h->ekf9, libm, h->ctrl, p, t.rpm ? t.rpm : h->s.m_rpm, dst, h->stream);
     if (fused != (int)hipErrorNotSupported) launch_check(fused, "isr launch");
@@ -243,7 +243,7 @@ static void isr_launches(fmskf_ctx *h, const TickIn &t, uint8_t *dst) {
     int e = 0;
     switch (h->cfg.model) {
       case FMSKF_MODEL_KF6: e = kf6_tick_launch(h, t, libm, true, true); break;
-      case FMSKF_MODEL_EKF9: e = launch_ekf9(h->s, t, h->ekf9, libm, true, true, h->stream); break;
+      case FMSKF_MODEL_EKF9: e = ekf9_tick_launch(h, t, libm, true, true); break;
       case FMSKF_MODEL_KF12D: e = launch_kf12d(h->s, t, h->kf12, true, true, h->stream); break;
     }
     launch_check(e, "tick kernel launch");
@@ -302,7 +302,7 @@ int fmskf_isr_tick_can(fmskf_handle h, const uint8_t *can_frames, const int16_t 
     if (h->cfg.model == FMSKF_MODEL_KF6 && isr_kf6_fused() && !h->gate_on && !in->kf6_rec && !in->rpm) {
       fused = launch_isr_kf6_can(h->s, t, h->kf6, libm, h->ctrl, ctrl_step_prm(h), dst, (const uint8_t *)f,
                                  (const int16_t *)s, h->cfg.motor_dir, h->stream);
-    } else if (h->cfg.model == FMSKF_MODEL_EKF9 && isr_kf6_fused() && !in->rpm) {
+    } else if (h->cfg.model == FMSKF_MODEL_EKF9 && isr_kf6_fused() && !h->rowgate_on && !in->rpm) {
       fused = launch_isr_ekf9_can(h->s, t, h->ekf9, libm, h->ctrl, ctrl_step_prm(h), dst, (const uint8_t *)f,
                                   (const int16_t *)s, h->cfg.motor_dir, h->stream);
     } else if (h->cfg.model == FMSKF_MODEL_RS && !in->rpm && !in->angle_sum) {

@@ -171,6 +171,12 @@ struct fmskf_ctx {
   // (ISR, tick + ensemble record) take their fallbacks.
   bool gate_on = false;
   fmskf::GateDev gate{};
+  // per-row innovation gate (fmskf_set_row_gate; EKF9 without FMSKF_CFG_COMP_POS, diagonal R):
+  // thresholds and the per-robot state planes, allocated when a row gate is first set.  While
+  // rowgate_on, every EKF9 measurement update goes through ekf9_tick_launch's gated kernels and
+  // the fused forms (ISR, tick + ensemble record) take their fallbacks.
+  bool rowgate_on = false;
+  fmskf::RowGateDev rowgate{};
   // fmskf_correct_pose: malformed entries of device fix lists, counted by the kernel
   // (fmskf_get_counters [3]); a word of its own, since DevState::counters is checkpointed whole
   unsigned long long *fix_ignored = nullptr;
@@ -405,6 +411,14 @@ inline int kf6_tick_launch(fmskf_ctx *h, const TickIn &t, bool libm, bool upd, b
 }
 // zero the gate state planes (no-op while none are allocated)
 void zero_gate(fmskf_ctx *h);
+// the EKF9 tick / correct / predict launch of a handle: the row-gated kernels while a row gate is
+// set and the call updates, the plain ones otherwise
+inline int ekf9_tick_launch(fmskf_ctx *h, const TickIn &t, bool libm, bool upd, bool pred) {
+  if (h->rowgate_on && upd) return launch_ekf9_rowgate(h->s, t, h->ekf9, h->rowgate, libm, pred, h->stream);
+  return launch_ekf9(h->s, t, h->ekf9, libm, upd, pred, h->stream);
+}
+// zero the row-gate state planes (no-op while none are allocated)
+void zero_rowgate(fmskf_ctx *h);
 void copy_out(fmskf_ctx *h, void *dst, const void *src, size_t bytes, uint32_t mem);
 void copy_planes_out(fmskf_ctx *h, void *dst, const void *src, size_t row, size_t dev_pitch,
                      size_t planes, uint32_t mem);

@@ -160,6 +160,13 @@ void zero_gate(fmskf_ctx *h) {
   hip_check(hipMemsetAsync(h->gate.nis, 0, h->s.n * 4, h->stream), "reset gate");
 }
 
+void zero_rowgate(fmskf_ctx *h) {
+  if (!h->rowgate.word) return;
+  hip_check(hipMemsetAsync(h->rowgate.word, 0, h->s.n * 8, h->stream), "reset row gate");
+  hip_check(hipMemsetAsync(h->rowgate.d2, 0, (size_t)FMSKF_EKF9_ROWS * h->rowgate.d2_pitch * 4, h->stream),
+            "reset row gate");
+}
+
 void ensure_motors(fmskf_ctx *h) {
   DevState &s = h->s;
   if (s.m_sum_lo) return;
@@ -230,6 +237,7 @@ void do_reset(fmskf_ctx *h) {
   if (s.imu_reg) zero_imu(h);
   if (s.m_sum_lo) zero_motors(h);
   zero_gate(h);  // the gate state restarts, its thresholds stay
+  zero_rowgate(h);
   if (h->ctrl_ready) {  // the control objects are static in the firmware too: zero, power off
     const CtrlDev &c = h->ctrl;
     hip_check(hipMemsetAsync(c.ax, 0, (size_t)3 * kAxF * c.pitch * 4, st), "reset ctrl");
@@ -368,7 +376,7 @@ void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, ui
   switch (h->cfg.model) {
     case FMSKF_MODEL_RS: e = launch_rs(h->s, t, libm, upd, pred, h->stream); break;
     case FMSKF_MODEL_KF6: e = kf6_tick_launch(h, t, libm, upd, pred); break;
-    case FMSKF_MODEL_EKF9: e = launch_ekf9(h->s, t, h->ekf9, libm, upd, pred, h->stream); break;
+    case FMSKF_MODEL_EKF9: e = ekf9_tick_launch(h, t, libm, upd, pred); break;
     case FMSKF_MODEL_KF12D: e = launch_kf12d(h->s, t, h->kf12, upd, pred, h->stream); break;
   }
   launch_check(e, "tick kernel launch");
@@ -870,6 +878,61 @@ int fmskf_get_gate(fmskf_handle h, float *nis, uint8_t *status, uint8_t *run, ui
         copy_out(h, rejects, scr, n * 4, mem);
         copy_out(h, status, scr + 4 * n, n, mem);
         copy_out(h, run, scr + 5 * n, n, mem);
+      }
+    }
+    finish_out(h, mem);
+  });
+}
+
+int fmskf_set_row_gate(fmskf_handle h, const fmskf_row_gate *g) {
+  return guarded([&] {
+    check_handle(h);
+    if (h->cfg.model != FMSKF_MODEL_EKF9 || (h->cfg.flags & FMSKF_CFG_COMP_POS) || !h->s.tile)
+      fail(FMSKF_ENOTSUP, "the row gate is for EKF9 without FMSKF_CFG_COMP_POS");
+    if (!ekf9_r_diagonal(h->ekf9.r))
+      fail(FMSKF_ENOTSUP, "the row gate needs a diagonal R (the sequential scalar update)");
+    if (h->capturing) fail(FMSKF_EINVAL, "row gate changed inside a graph capture");
+    if (!g) {
+      h->rowgate_on = false;
+      return;
+    }
+    for (int a = 0; a < FMSKF_EKF9_ROWS; a++)
+      if (!(g->d2_max[a] > 0.0f)) fail(FMSKF_EINVAL, "d2_max entries must be > 0 (+INFINITY: never reject)");
+    if (g->max_consecutive > 255) fail(FMSKF_EINVAL, "max_consecutive above 255 (the runs saturate there)");
+    if (g->flags & ~FMSKF_ROW_GATE_D2) fail(FMSKF_EINVAL, "unknown row gate flags");
+    DeviceGuard dg(h->cfg.device);
+    if (!h->rowgate.word) {
+      h->rowgate.word = h->alloc<uint64_t>(h->s.n);
+      h->rowgate.d2_pitch = h->s.pitch;
+      h->rowgate.d2 = h->alloc<float>((size_t)FMSKF_EKF9_ROWS * h->s.pitch);
+    }
+    if (!h->rowgate_on) zero_rowgate(h);  // a newly set gate starts from a zero gate state
+    for (int a = 0; a < FMSKF_EKF9_ROWS; a++) h->rowgate.d2_max[a] = g->d2_max[a];
+    h->rowgate.max_run = g->max_consecutive;
+    h->rowgate.flags = g->flags;
+    h->rowgate_on = true;
+  });
+}
+
+int fmskf_get_row_gate(fmskf_handle h, uint8_t *status, uint8_t *run, float *d2, uint32_t mem) {
+  return guarded([&] {
+    check_handle(h);
+    if (!h->rowgate_on) fail(FMSKF_EINVAL, "no row gate set (fmskf_set_row_gate)");
+    if (d2 && !(h->rowgate.flags & FMSKF_ROW_GATE_D2))
+      fail(FMSKF_EINVAL, "d2 is kept only with FMSKF_ROW_GATE_D2");
+    if (mem != FMSKF_MEM_HOST && mem != FMSKF_MEM_DEVICE) fail(FMSKF_EINVAL, "bad mem flag");
+    DeviceGuard dg(h->cfg.device);
+    const uint64_t n = h->s.n;
+    const size_t rows = FMSKF_EKF9_ROWS;
+    copy_planes_out(h, d2, h->rowgate.d2, n * 4, h->rowgate.d2_pitch * 4, rows, mem);
+    if (status || run) {
+      if (mem == FMSKF_MEM_DEVICE) {
+        launch_check(launch_rowgate_unpack(h->rowgate.word, n, status, run, h->stream), "row gate readout");
+      } else {  // unpacked into device scratch: status [6][N], run [6][N]
+        uint8_t *scr = (uint8_t *)h->out_for(2 * rows * n);
+        launch_check(launch_rowgate_unpack(h->rowgate.word, n, scr, scr + rows * n, h->stream), "row gate readout");
+        copy_out(h, status, scr, rows * n, mem);
+        copy_out(h, run, scr + rows * n, rows * n, mem);
       }
     }
     finish_out(h, mem);

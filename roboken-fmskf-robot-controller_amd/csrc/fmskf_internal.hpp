@@ -172,6 +172,19 @@ struct GateDev {
   uint32_t max_run;
 };
 constexpr uint32_t kGateRunShift = 2, kGateRunMax = 255, kGateRejShift = 10, kGateRejMax = (1u << 22) - 1u;
+// The per-row innovation gate of an EKF9 handle (fmskf_set_row_gate): its configuration and the
+// per-robot state, read and written by the row-gated tick kernels alone (kernels_rowgate.hip; an
+// argument struct of their own, RowGateArgs).  word [N]: bits 0-11 the six rows' 2-bit statuses,
+// bits 12-59 their 8-bit runs (kf_generic.hpp kRowGate*); d2 [6][d2_pitch]: every row's last
+// evaluated normalised innovation squared, stored only with FMSKF_ROW_GATE_D2.
+struct RowGateDev {
+  uint64_t *word;
+  float *d2;
+  uint64_t d2_pitch;
+  float d2_max[6];
+  uint32_t max_run;
+  uint32_t flags;
+};
 // One fmskf_correct_pose call as its kernel sees it (kernels_fix.hip; an argument struct of its
 // own, like the gate's): the sorted fix list and the optional per-fix outputs (device pointers),
 // the fix noise narrowed to fp32, the call's threshold and the measurement dimension
@@ -409,6 +422,12 @@ int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_
 int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st);
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
                 bool pred, hipStream_t st, int *ens_nb = nullptr);
+// the row-gated EKF9 measurement update (kernels_rowgate.hip), with the predict (pred) or alone;
+// tiled plain state (no FMSKF_CFG_COMP_POS), diagonal R, no fused ensemble record
+int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p, const RowGateDev &g,
+                        bool libm, bool pred, hipStream_t st);
+// the row-gate words unpacked into status [6][N], run [6][N] (device pointers, either may be null)
+int launch_rowgate_unpack(const uint64_t *word, uint64_t n, uint8_t *status, uint8_t *run, hipStream_t st);
 int launch_kf12d(const DevState &s, const TickIn &in, const Kf12dParams &p, bool upd, bool pred,
                  hipStream_t st, int *ens_nb = nullptr);
 int launch_wt901(const DevState &s, const uint8_t *bytes, uint32_t stride, const uint32_t *len,

@@ -387,6 +387,73 @@ __device__ __forceinline__ void kf_update_seq(T (&x)[N], T (&P)[NP], T (&y)[M], 
   comp_norm<CXM, CPM>(x, P, clo);
 }
 
+// The per-row gate word of kf_update_seq_gated (fmskf_set_row_gate): bits 0-11 the rows' 2-bit
+// statuses (FMSKF_GATE_*, row a at bit 2a), bits 12-59 their 8-bit runs of consecutive
+// rejections (row a at bit 12 + 8a, saturating at 255)
+constexpr uint32_t kRowGateRunShift = 12, kRowGateRunMax = 255;
+constexpr uint64_t kRowGateStatusMask = 0xFFFull;
+
+// kf_update_seq with every scalar row behind its own innovation gate.  At row a, hp, s, si and
+// g = y_a / s are formed as in kf_update_seq, then d2 = y_a * g (one rounded product: the row's
+// normalised innovation squared), forced = max_run > 0 && run_a >= max_run and apply = forced ||
+// d2 <= d2_max[a] (a NaN d2 is rejected unless forced).  An applied row runs the operations of
+// kf_update_seq's row; a rejected one touches neither x, lo, P nor the later innovations: a
+// per-lane branch around the three sub-loops.  All rows applied is kf_update_seq bit for bit;
+// a rejected row equals r_aa = +inf (si = 0: every term an exact zero) up to the sign of a zero.
+// word: the rows' statuses and runs (above), updated; d2o: every row's d2.  No compensated
+// entries but the state CI.
+template <class Md, int CI = -1, typename T = typename Md::T, int N = Md::N, int M = Md::M,
+          int NP = Md::N *(Md::N + 1) / 2>
+__device__ __forceinline__ void kf_update_seq_gated(T (&x)[N], T (&P)[NP], T (&y)[M], const T *R,
+                                                    const T *d2_max, uint32_t max_run, uint64_t &word,
+                                                    T (&d2o)[M], T *lo = nullptr) {
+  static_assert(2 * M <= (int)kRowGateRunShift && kRowGateRunShift + 8 * M <= 64, "rows per gate word");
+  uint64_t nw = 0;
+#pragma unroll
+  for (int a = 0; a < M; a++) {
+    T hp[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+      T v = P[pk(Md::h1(a), j)];
+      if (Md::h2(a) >= 0) v = v + P[pk(Md::h2(a) < 0 ? 0 : Md::h2(a), j)];
+      hp[j] = v;
+    }
+    T s = hp[Md::h1(a)];
+    if (Md::h2(a) >= 0) s = s + hp[Md::h2(a) < 0 ? 0 : Md::h2(a)];
+    s = s + R[pk(a, a)];
+    const T si = (T)1 / s;
+    const T g = y[a] * si;
+    const T d2 = y[a] * g;
+    const uint32_t run = (uint32_t)(word >> (kRowGateRunShift + 8 * a)) & kRowGateRunMax;
+    const bool forced = max_run > 0 && run >= max_run;
+    const bool apply = forced || d2 <= d2_max[a];
+    if (apply) {
+#pragma unroll
+      for (int j = 0; j < N; j++) {
+        if (j == CI) th_add(x[j], *lo, hp[j] * g);
+        else x[j] = dfma<T>(hp[j], g, x[j]);
+      }
+#pragma unroll
+      for (int b = a + 1; b < M; b++) {
+        T h = hp[Md::h1(b)];
+        if (Md::h2(b) >= 0) h = h + hp[Md::h2(b) < 0 ? 0 : Md::h2(b)];
+        y[b] = dfma<T>(-h, g, y[b]);
+      }
+#pragma unroll
+      for (int i = 0; i < N; i++) {
+        const T t = hp[i] * si;
+#pragma unroll
+        for (int j = 0; j <= i; j++) P[pk(i, j)] = dfma<T>(-t, hp[j], P[pk(i, j)]);
+      }
+    }
+    const uint32_t status = forced ? FMSKF_GATE_FORCED : apply ? FMSKF_GATE_ACCEPTED : FMSKF_GATE_REJECTED;
+    const uint32_t nrun = apply ? 0u : min(run + 1u, kRowGateRunMax);
+    nw |= ((uint64_t)status << (2 * a)) | ((uint64_t)nrun << (kRowGateRunShift + 8 * a));
+    d2o[a] = d2;
+  }
+  word = nw;
+}
+
 // P <- F P F^T + Q, F = I + Fv(i,k) on the compile-time pattern Md::pat
 // SKIPQ: an exactly-zero Q entry is not added (a wave-uniform branch on the kernel-argument Q;
 // the canonical KF12D order, oracle orc_kf12d_tick: t + 0 only differs from t for t = -0)

@@ -80,6 +80,15 @@ class Gate(C.Structure):
     _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
 
 
+# fmskf_set_row_gate (EKF9): FMSKF_EKF9_ROWS, FMSKF_ROW_GATE_D2
+EKF9_ROWS = 6
+ROW_GATE_D2 = 1
+
+
+class RowGate(C.Structure):
+    _fields_ = [("d2_max", C.c_float * EKF9_ROWS), ("max_consecutive", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class PoseFix(C.Structure):
     _fields_ = [("robot", C.c_uint32), ("x_m", C.c_float), ("y_m", C.c_float), ("theta_rad", C.c_float)]
 
@@ -138,6 +147,8 @@ SIGNATURES = {
     "fmskf_get_counters": (C.c_int, [_H, _P, C.c_uint32]),
     "fmskf_set_gate": (C.c_int, [_H, C.POINTER(Gate)]),
     "fmskf_get_gate": (C.c_int, [_H, _P, _P, _P, _P, C.c_uint32]),
+    "fmskf_set_row_gate": (C.c_int, [_H, C.POINTER(RowGate)]),
+    "fmskf_get_row_gate": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_correct_pose": (C.c_int, [_H, _P, C.c_uint64, C.POINTER(PoseFixParams), _P, _P, C.c_uint32]),
     "fmskf_ensemble_record_len": (C.c_int, [_H, C.POINTER(C.c_uint32)]),
     "fmskf_ensemble_partial": (C.c_int, [_H, _P, C.c_uint32]),

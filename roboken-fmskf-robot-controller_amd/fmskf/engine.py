@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib
 from ._lib import (MEM_DEVICE, MEM_HOST, MODEL_EKF9, MODEL_KF6, MODEL_KF12D, MODEL_NAMES,
                    MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FIX_HEADING, FmskfError,
-                   Gate, PoseFixParams, TickInputs, check, load)
+                   EKF9_ROWS, Gate, PoseFixParams, ROW_GATE_D2, RowGate, TickInputs, check, load)
 
 # fmskf_vehicle_info (include/fmskf.h): the VehicleInfo message layout, 84 bytes
 VEHICLE_INFO_DTYPE = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("pos_theta", "<f4"),
@@ -245,6 +245,37 @@ class Engine:
                    run=np.empty(self.n, np.uint8), rejects=np.empty(self.n, np.uint32))
         check(load().fmskf_get_gate(self.h, *(a.ctypes.data_as(C.c_void_p) for a in out.values()), MEM_HOST),
               "get_gate")
+        return out
+
+    # ------------------------------------------------------------------ per-row innovation gate
+    def set_row_gate(self, d2_max=None, max_consecutive=0, record_d2=False):
+        """fmskf_set_row_gate (EKF9, diagonal R): row a of the sequential update (heading, gyro z,
+        ax, ay, vbx, vby) is skipped when its normalised innovation squared exceeds d2_max[a] (a
+        scalar: the same threshold for every row; float('inf'): never); a row rejected
+        max_consecutive times in a row is then applied whatever its d2 (0: never).  record_d2
+        keeps every row's last d2 for get_row_gate.  d2_max=None turns the row gate off."""
+        if d2_max is None:
+            check(load().fmskf_set_row_gate(self.h, None), "set_row_gate")
+            return
+        g = RowGate()
+        v = np.broadcast_to(np.asarray(d2_max, np.float32), (EKF9_ROWS,))
+        for a in range(EKF9_ROWS):
+            g.d2_max[a] = float(v[a])
+        g.max_consecutive = int(max_consecutive)
+        g.flags = ROW_GATE_D2 if record_d2 else 0
+        check(load().fmskf_set_row_gate(self.h, C.byref(g)), "set_row_gate")
+        self._row_d2 = bool(record_d2)
+
+    def get_row_gate(self):
+        """fmskf_get_row_gate: dict of status [6, N] uint8 (GATE_NONE / ACCEPTED / REJECTED /
+        FORCED), run [6, N] uint8 (consecutive rejections) and, when the gate was set with
+        record_d2, d2 [6, N] float32"""
+        out = dict(status=np.empty((EKF9_ROWS, self.n), np.uint8), run=np.empty((EKF9_ROWS, self.n), np.uint8))
+        if getattr(self, "_row_d2", False):
+            out["d2"] = np.empty((EKF9_ROWS, self.n), np.float32)
+        pd = out["d2"].ctypes.data_as(C.c_void_p) if "d2" in out else None
+        check(load().fmskf_get_row_gate(self.h, out["status"].ctypes.data_as(C.c_void_p),
+                                        out["run"].ctypes.data_as(C.c_void_p), pd, MEM_HOST), "get_row_gate")
         return out
 
     # ------------------------------------------------------------------ absolute pose fixes

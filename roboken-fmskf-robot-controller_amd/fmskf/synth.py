@@ -222,6 +222,31 @@ def inject_outliers(yaw_deg, rpm, seed: int = SEED, start: int = 20, yaw_share: 
     return yaw, out, kind
 
 
+def inject_outliers_ekf9(raw, seed: int = SEED, start: int = 20, share: float = 0.05):
+    """Measurement outliers for the EKF9 row gate (fmskf_set_row_gate), on a copy of
+    Trajectory.ekf9_raw() ([T,N,8] int16: Yaw, GZ, AX, AY registers + four rpm): from tick `start`
+    on, every tick three disjoint `share`s of the robots are hit: one reads a Yaw register off by
+    a uniform integer in +-728 counts (+-4 degrees: a WT901 heading glitch), one reads one wheel's
+    rpm raised by a uniform integer in [0, 30000) (a slipping wheel), one reads an AX register off
+    by a uniform integer in +-16000 counts (an accelerometer spike); all clipped to int16.
+    Returns (raw, kind [T,N] uint8: 0 clean, 1 yaw, 2 rpm, 3 ax)."""
+    rng = np.random.default_rng([seed, 0x6A7E, 9])
+    T, n = raw.shape[:2]
+    u = rng.random((T, n))
+    u[:start] = 1.0
+    kind = np.where(u < share, 1, np.where(u < 2 * share, 2, np.where(u < 3 * share, 3, 0))).astype(np.uint8)
+    out = raw.astype(np.int64)
+    dyaw = rng.integers(-728, 729, (T, n))
+    wheel = rng.integers(0, 4, (T, n))
+    drpm = rng.integers(0, 30000, (T, n))
+    dax = rng.integers(-16000, 16001, (T, n))
+    out[..., 0] += np.where(kind == 1, dyaw, 0)
+    t_i, r_i = np.nonzero(kind == 2)
+    out[t_i, r_i, 4 + wheel[t_i, r_i]] += drpm[t_i, r_i]
+    out[..., 2] += np.where(kind == 3, dax, 0)
+    return np.ascontiguousarray(np.clip(out, -32768, 32767).astype(np.int16)), kind
+
+
 def pose_fixes(traj, t, every: int = 32, start: int = 8, sigma: float = 1e-2, outlier_share: float = 0.05,
                outlier_start: int = 40, seed: int = SEED):
     """Absolute pose fixes (a ceiling camera, UWB: fmskf_correct_pose) for the call made before

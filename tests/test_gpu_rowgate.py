@@ -1,0 +1,470 @@
+"""The EKF9 per-row innovation gate (fmskf_set_row_gate / fmskf_get_row_gate;
+csrc/kernels_rowgate.hip) on the GPU: the row-gated tick against the oracle run with +inf on the
+rejected rows' R (tests/rowgate_ref.py), the decisions and the d2 planes against the float64
+sequential update on the pre-tick state, monitor-only mode, every kernel form and fused entry
+point against the single gated tick, the lifecycle (reset, checkpoint) and the argument rules.
+
+Sizes: N = 1, 300 (two 256-robot chunks, the second partial) and 4113 (17 chunks, an odd count
+with a partial last: the two-robots-per-lane kernel meets a block without a partner chunk and
+clamped lanes)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import fmskf
+from fmskf import Engine
+
+import rowgate_ref as ref
+from rowgate_ref import ALL, BAND, D2_MAX, ROWS, NONE, ACC, REJ, FRC
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = (1, 300, 4113)
+T = 60
+MAXC = 3        # max_consecutive of the main runs: small, so that FORCED occurs
+START = 8       # first tick with outliers in the main runs
+TABLE, LIBM = fmskf.TRIG_TABLE512, fmskf.TRIG_LIBM
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def _state10(e):
+    """(x10 [10,n] with the heading's low part in row 9, P [45,n]) of an EKF9 engine"""
+    x, P = e.get_state()
+    return np.concatenate([x, e.get_state_lo()[:1]]), P
+
+
+def _same_gate(ga, gb, what):
+    assert set(ga) == set(gb), what
+    for k in ga:
+        assert np.array_equal(_bits(ga[k]), _bits(gb[k])), f"{what}: {k}"
+
+
+def _same_state(a, b, what):
+    (xa, Pa), (xb, Pb) = _state10(a), _state10(b)
+    assert np.array_equal(_bits(xa), _bits(xb)), f"{what}: x / heading low part"
+    assert np.array_equal(_bits(Pa), _bits(Pb)), f"{what}: P"
+
+
+_RUNS = {}
+
+
+def _main_run(orc, n, trig, masked):
+    """One row-gated run of n robots over T ticks with FMSKF_ROW_GATE_D2, computed once per (n,
+    trig, masked) and shared.  Per tick: the GPU's gate readout; the float64 d2 of every row on
+    the GPU's pre-tick state with the GPU's own decisions for the earlier rows; and the comparison
+    of the GPU's post-tick state with the oracle's, run from the same pre-tick state with +inf on
+    the rows the GPU did not apply.  Forms in rotation: tick, correct + predict as two calls, tick.
+    TABLE512: x, the heading's low part and P np.array_equal the oracle's, the robots with every
+    row applied bit for bit.  LIBM: the device's sinf / cosf differ from the oracle's libm by ulps
+    (tests/test_gpu_parity.py test_ekf9_libm_within_tolerance), which reaches px, py and P through
+    the predict alone: the update (checked after the correct call of the two-call form) and the
+    post-tick x[2..8] and low part are np.array_equal, px, py and P within the project's LIBM
+    tolerance (rtol 1e-5)."""
+    key = (n, trig, masked)
+    if key in _RUNS:
+        return _RUNS[key]
+    exact = trig == TABLE
+    raw, _, _ = ref.inputs(n, T, seed=5000 + n, start=START)
+    valid = (np.random.default_rng(n).random((T, n)) > 0.2).astype(np.uint8) if masked else None
+    r = dict(d2_64=np.zeros((T, ROWS, n)), d2=np.zeros((T, ROWS, n), np.float32),
+             status=np.zeros((T, ROWS, n), np.uint8), run=np.zeros((T, ROWS, n), np.uint8),
+             has=np.ones((T, n), bool), bad=[])
+
+    def differs(x10, P, xo, Po, full):
+        p63 = (pat == ALL) & has
+        if not (np.array_equal(x10[2:], xo[2:]) and np.array_equal(_bits(x10[2:, p63]), _bits(xo[2:, p63]))):
+            return True
+        if exact or not full:
+            return not (np.array_equal(x10[:2], xo[:2]) and np.array_equal(P, Po) and
+                        np.array_equal(_bits(x10[:2, p63]), _bits(xo[:2, p63])) and
+                        np.array_equal(_bits(P[:, p63]), _bits(Po[:, p63])))
+        return not (np.allclose(x10[:2], xo[:2], rtol=1e-5, atol=1e-6) and np.allclose(P, Po, rtol=1e-5, atol=1e-9))
+
+    with Engine("ekf9", n, trig=trig) as e:
+        e.set_row_gate(D2_MAX, MAXC, record_d2=True)
+        g = e.get_row_gate()
+        assert not g["status"].any() and not g["run"].any() and not g["d2"].any()
+        prev_run = np.zeros((ROWS, n), np.uint8)
+        for t in range(T):
+            x0, P0 = _state10(e)
+            kw = dict(raw=raw[t]) if valid is None else dict(raw=raw[t], valid=valid[t])
+            has = np.ones(n, bool) if valid is None else valid[t] != 0
+            split = t % 3 == 1
+            if split:
+                e.correct(**kw)
+                xc, Pc = _state10(e)
+                e.predict()
+            else:
+                e.tick(**kw)
+            g = e.get_row_gate()
+            applied = np.isin(g["status"], (ACC, FRC))
+            pat = ref.pattern(applied)
+            u = ref.update64(orc, x0, P0, raw[t], D2_MAX, MAXC, prev_run, apply=applied)
+            r["d2_64"][t], r["has"][t] = u["d2"], has
+            for k in ("d2", "status", "run"):
+                r[k][t] = g[k]
+            if split:  # the update alone: no trig in it
+                xo, Po = x0.copy(), P0.copy()
+                ref.oracle_tick(orc, xo, Po, raw[t], applied, has, trig, do_predict=False)
+                if differs(xc, Pc, xo, Po, False):
+                    r["bad"].append((t, "correct"))
+            xo, Po = x0.copy(), P0.copy()
+            ref.oracle_tick(orc, xo, Po, raw[t], applied, has, trig)
+            x1, P1 = _state10(e)
+            if differs(x1, P1, xo, Po, True):
+                r["bad"].append((t, "tick"))
+            prev_run = g["run"]
+        r["nan_count"] = e.get_counters()[0]
+    _RUNS[key] = r
+    return r
+
+
+# ---------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("trig", [TABLE, LIBM])
+@pytest.mark.parametrize("n", SHAPES)
+def test_rowgated_tick_against_oracle(orc, n, trig, masked):
+    """every tick: x, P and the heading's low part equal the oracle's, run from the same state with
+    +inf on the rows the GPU did not apply (see _main_run); counter [0] stays 0"""
+    r = _main_run(orc, n, trig, masked)
+    assert not r["bad"], f"n={n}: state differs from the oracle's at {r['bad'][:8]}"
+    assert r["nan_count"] == 0
+    if n >= 300:  # the run exercises every outcome, and mixed patterns
+        for s in (ACC, REJ, FRC) + ((NONE,) if masked else ()):
+            assert np.any(r["status"] == s), s
+        mixed = np.any(r["status"] == REJ, axis=1) & np.any(r["status"] == ACC, axis=1)
+        assert mixed.any()
+
+
+# ---------------------------------------------------------------------------- 2
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("n", SHAPES)
+def test_decisions_against_float64(orc, n, masked):
+    """outside the 1e-3 band around d2_max every row's status is the rule's on the float64 d2
+    (FORCED from the GPU's own previous run of that row, max_consecutive = 3); at most 1e-3 of the
+    evaluated rows lie in the band; the runs follow the statuses; a robot without a measurement
+    reads NONE in every row and keeps its runs and its d2; the d2 planes agree with float64 at
+    rtol 1e-3, atol 1e-4 (measured on an MI355X near the threshold: 9.9e-6 at most, N = 4113 with
+    a mask; at most 17 of 1.48 million evaluated rows in the band)"""
+    r = _main_run(orc, n, TABLE, masked)
+    prev_run = np.zeros((ROWS, n), np.uint8)
+    prev_d2 = np.zeros((ROWS, n), np.float32)
+    in_band = evaluated = 0
+    worst = 0.0
+    for t in range(T):
+        has, st, d64 = r["has"][t], r["status"][t], r["d2_64"][t]
+        h6 = np.broadcast_to(has, (ROWS, n))
+        want_apply, forced = ref.decide(d64, prev_run, D2_MAX, MAXC)
+        want, _ = ref.status_run(want_apply, forced, prev_run)
+        band = h6 & ~forced & (np.abs(d64 - D2_MAX) <= BAND * D2_MAX)
+        in_band += int(np.count_nonzero(band))
+        evaluated += int(np.count_nonzero(h6))
+        cmp = h6 & ~band
+        assert np.array_equal(st[cmp], want[cmp]), f"n={n} t={t}: decision"
+        assert np.all(st[~h6] == NONE) and np.all(st[h6] != NONE), f"n={n} t={t}: NONE"
+        assert np.array_equal(st == FRC, h6 & forced), f"n={n} t={t}: forced"
+        _, run_want = ref.status_run(np.isin(st, (ACC, FRC)), st == FRC, prev_run, has)
+        assert np.array_equal(r["run"][t], run_want), f"n={n} t={t}: run"
+        assert np.array_equal(_bits(r["d2"][t][~h6]), _bits(prev_d2[~h6])), f"n={n} t={t}: d2 kept"
+        np.testing.assert_allclose(r["d2"][t][h6], d64[h6], rtol=1e-3, atol=1e-4, err_msg=f"n={n} t={t}: d2")
+        near = h6 & (d64 > D2_MAX / 4) & (d64 < 4 * D2_MAX)
+        if near.any():
+            worst = max(worst, float((np.abs(r["d2"][t][near] - d64[near]) / d64[near]).max()))
+        prev_run, prev_d2 = r["run"][t], r["d2"][t]
+    print(f"n={n}: d2 fp32 against float64 near the threshold: largest relative error {worst:.3e}; "
+          f"{in_band} of {evaluated} evaluated rows in the band")
+    assert in_band <= 1e-3 * evaluated
+
+
+# ---------------------------------------------------------------------------- 3
+@pytest.mark.parametrize("n", SHAPES)
+def test_monitor_only(orc, n, tmp_path):
+    """all d2_max = inf, max_consecutive = 0: the state equals an ungated engine's bit for bit,
+    every row of a measured robot is ACCEPTED and d2 is reported; a gate set and cleared again
+    leaves no trace in the state or in the checkpoint bytes"""
+    Tm = 12
+    raw, _, _ = ref.inputs(n, Tm, seed=8000 + n, start=4)
+    valid = (np.random.default_rng(n + 5).random((Tm, n)) > 0.2).astype(np.uint8)
+    with Engine("ekf9", n) as e, Engine("ekf9", n) as p, Engine("ekf9", n) as c:
+        e.set_row_gate(float("inf"), 0, record_d2=True)
+        c.set_row_gate(D2_MAX, 1)
+        c.set_row_gate(None)
+        for t in range(Tm):
+            x0, P0 = _state10(e)
+            u = ref.update64(orc, x0, P0, raw[t], np.inf)
+            kw = dict(raw=raw[t], valid=valid[t]) if t % 2 else dict(raw=raw[t])
+            has = valid[t] != 0 if t % 2 else np.ones(n, bool)
+            for eng in (e, p, c):
+                eng.tick(**kw)
+            g = e.get_row_gate()
+            assert np.array_equal(g["status"], np.where(has[None, :], ACC, NONE) * np.ones((ROWS, 1), np.uint8)), t
+            assert not g["run"].any()
+            np.testing.assert_allclose(g["d2"][:, has], u["d2"][:, has], rtol=1e-3, atol=1e-4)
+            _same_state(e, p, f"monitor-only t={t}")
+        _same_state(c, p, "gate set and cleared")
+        files = []
+        for k, eng in enumerate((p, c)):
+            f = tmp_path / f"m{k}.ck"
+            eng.save_state(str(f))
+            files.append(f.read_bytes())
+        assert files[0] == files[1]
+        with pytest.raises(fmskf.FmskfError):
+            c.get_row_gate()
+
+
+# ---------------------------------------------------------------------------- 4
+def _variant_result():
+    """row-gated single ticks (a valid mask on every other tick), the same ticks as tick_many
+    launches of T = 5, and as correct + predict, at every size and both trig policies: the final
+    state and gate readout, which must agree with each other here and with every other kernel
+    selection (FMSKF_EKF9_VARIANT, FMSKF_STATE_NT)"""
+    out = {}
+    Tv = 15
+    for n in SHAPES:
+        raw, _, _ = ref.inputs(n, Tv, seed=9100 + n, start=4)
+        valid = (np.random.default_rng(n + 9).random((Tv, n)) > 0.2).astype(np.uint8)
+        valid[::2] = 1
+        for trig in (TABLE, LIBM):
+            with Engine("ekf9", n, trig=trig) as a, Engine("ekf9", n, trig=trig) as b, \
+                    Engine("ekf9", n, trig=trig) as c:
+                for e in (a, b, c):
+                    e.set_row_gate(D2_MAX, MAXC, record_d2=True)
+                for t in range(Tv):
+                    a.tick(raw=raw[t], valid=valid[t])
+                    c.correct(raw=raw[t], valid=valid[t])
+                    c.predict()
+                for t0 in range(0, Tv, 5):
+                    b.tick_many(5, raw=raw[t0:t0 + 5], valid=valid[t0:t0 + 5])
+                ga = a.get_row_gate()
+                for e, what in ((b, "tick_many"), (c, "correct + predict")):
+                    _same_state(a, e, f"n={n} trig={trig} {what}")
+                    _same_gate(ga, e.get_row_gate(), f"n={n} trig={trig} {what}")
+                x, P = _state10(a)
+                out.update({f"x{n}_{trig}": x, f"P{n}_{trig}": P, **{f"{k}{n}_{trig}": v for k, v in ga.items()}})
+    return out
+
+
+def test_forms_agree():
+    res = _variant_result()
+    assert np.any(res[f"status4113_{TABLE}"] == REJ) and np.any(res[f"run4113_{TABLE}"] > 0)
+    _RUNS["variant"] = res
+
+
+@pytest.mark.parametrize("force", [{"FMSKF_EKF9_VARIANT": "2"}, {"FMSKF_EKF9_VARIANT": "4"}, {"FMSKF_STATE_NT": "1"}])
+def test_rowgate_kernel_variants_bitexact(force, tmp_path):
+    """the other kernel forms (two robots per lane / one per lane forced, the non-temporal state),
+    forced in a child process as test_gpu_gate.py's forced-variant test does: the same state and
+    gate readout as this process's selection, bit for bit"""
+    here = _RUNS.get("variant") or _variant_result()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    path = str(tmp_path / "variant.npz")
+    script = ("import sys, numpy as np\nsys.path[:0] = sys.argv[1:4]\nimport test_gpu_rowgate as m\n"
+              "np.savez(sys.argv[4], **m._variant_result())\nprint('rowgate variants ok')\n")
+    out = subprocess.run([sys.executable, "-c", script, root, os.path.join(root, "roboken-fmskf-robot-controller_amd"),
+                          os.path.join(root, "tests"), path],
+                         capture_output=True, text=True, timeout=240, env=dict(os.environ, **force))
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert "rowgate variants ok" in out.stdout
+    got = np.load(path)
+    assert set(got.files) == set(here)
+    for k in here:
+        assert np.array_equal(_bits(got[k]), _bits(here[k])), (force, k)
+
+
+# ---------------------------------------------------------------------------- 5
+def test_fused_entry_points_take_the_gated_tick():
+    """with a row gate set, isr_tick, isr_tick_can and tick_ensemble leave the estimator state and
+    the gate state the gated tick leaves; the ISRs run split (counters [1], [2]) and their frames
+    and currents are the separate calls'"""
+    from fmskf.synth import Trajectory, inject_outliers_ekf9
+    n, Tf = 4113, 10
+    tr = Trajectory(n, Tf, seed=66)
+    raw, _ = inject_outliers_ekf9(tr.ekf9_raw(), seed=66, start=3)
+    rpm = np.ascontiguousarray(tr.rpm)
+    vel = np.zeros((3, n), np.float32)
+    vel[0] = 200.0
+    acl = np.full((3, n), 1000.0, np.float32)
+    jrk = np.full((3, n), 10000.0, np.float32)
+    names = ("tick", "isr", "ens", "can_ref", "can", "ens_async")
+    eng = {k: Engine("ekf9", n) for k in names}
+    try:
+        for e in eng.values():
+            e.set_row_gate(D2_MAX, MAXC, record_d2=True)
+            e.set_power(None)
+            e.set_target_vel(vel, acl, jrk)
+        for t in range(Tf):
+            eng["tick"].tick(raw=raw[t])
+            eng["tick"].control(rpm[t])
+            f_ref = eng["tick"].can_tx()
+            f_isr = eng["isr"].isr_tick(raw=raw[t], rpm=rpm[t])
+            assert np.array_equal(f_ref, f_isr), t
+            r_fused = eng["ens"].tick_ensemble(raw=raw[t])
+            r_alone = eng["ens"].ensemble_partial()
+            assert r_fused[0] == n
+            np.testing.assert_allclose(r_fused, r_alone, rtol=1e-9, atol=1e-12)
+            eng["ens_async"].tick_ensemble_begin(raw=raw[t])
+            eng["ens_async"].ensemble_end()
+            frames, stamps = tr.can_frames(t)
+            eng["can_ref"].ingest_can(frames, stamps)
+            eng["can_ref"].tick(raw=raw[t])
+            eng["can_ref"].control()
+            f_cref = eng["can_ref"].can_tx()
+            f_can = eng["can"].isr_tick_can(frames, stamps, raw=raw[t])
+            assert np.array_equal(f_cref, f_can), t
+        g = eng["tick"].get_row_gate()
+        assert np.any(g["status"] == REJ)
+        for k in ("isr", "ens", "ens_async", "can_ref", "can"):
+            _same_state(eng["tick"], eng[k], k)
+            _same_gate(g, eng[k].get_row_gate(), k)
+        for a, b in (("tick", "isr"), ("can_ref", "can")):
+            ga, gb = eng[a].get_ctrl(), eng[b].get_ctrl()
+            for k in ("vel_tgt", "curr", "wheel_tgt", "wheel_ctrl"):
+                assert np.array_equal(_bits(ga[k]), _bits(gb[k])), (b, k)
+        assert eng["isr"].get_counters()[1:3] == [0, Tf]
+        assert eng["can"].get_counters()[1:3] == [Tf, Tf]
+        assert eng["tick"].get_counters()[1:3] == [0, 0]
+    finally:
+        for e in eng.values():
+            e.close()
+
+
+def test_captured_rowgated_tick():
+    """a row-gated tick on device pointers captured into a graph and replayed three times equals
+    three direct calls"""
+    import torch
+    n = 4113
+    raw, _, _ = ref.inputs(n, 10, seed=91, start=2)
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st), Engine("ekf9", n) as a, Engine("ekf9", n) as b:
+        for e in (a, b):
+            e.set_stream(st)
+            e.set_row_gate(D2_MAX, MAXC, record_d2=True)
+        dr = torch.empty((n, 8), dtype=torch.int16, device="cuda")
+        for t in range(7):  # direct ticks first, so that the replays start from a converged filter
+            dr.copy_(torch.from_numpy(raw[t]))
+            a.tick(raw=dr)
+            b.tick(raw=dr)
+        b.graph_begin()
+        with pytest.raises(fmskf.FmskfError) as ei:
+            b.set_row_gate(None)  # the gate cannot change inside a capture
+        assert ei.value.code == 1
+        b.tick(raw=dr)
+        b.graph_end()
+        for t in range(7, 10):
+            dr.copy_(torch.from_numpy(raw[t]))
+            a.tick(raw=dr)
+            b.graph_launch(1)
+        st.synchronize()
+        _same_state(a, b, "graph")
+        _same_gate(a.get_row_gate(), b.get_row_gate(), "graph")
+        assert np.any(a.get_row_gate()["status"] == REJ)
+
+
+# ---------------------------------------------------------------------------- 6
+def test_lifecycle(tmp_path):
+    n, T1, T2 = 4113, 14, 8
+    raw, _, _ = ref.inputs(n, T1 + T2, seed=123, start=3)
+    with Engine("ekf9", n) as a, Engine("ekf9", n) as b, Engine("ekf9", n) as c, Engine("ekf9", n) as d:
+        for e in (a, b, d):
+            e.set_row_gate(D2_MAX, MAXC, record_d2=True)
+        with pytest.raises(fmskf.FmskfError) as ei:
+            c.get_row_gate()  # no row gate set
+        assert ei.value.code == 1
+        for t in range(T1):
+            for e in (a, c, d):
+                e.tick(raw=raw[t])
+        ga = a.get_row_gate()
+        assert ga["run"].any() and ga["d2"].any() and np.any(ga["status"] == REJ)
+        # set_state leaves the gate state alone; changing the thresholds of a set gate too
+        x, P = a.get_state()
+        lo = a.get_state_lo()
+        a.set_state(x, P)
+        a.set_state_lo(lo)
+        a.set_row_gate([D2_MAX] * ROWS, MAXC, record_d2=True)
+        _same_gate(ga, a.get_row_gate(), "set_state")
+        # save / load: the gate state travels, and the run continues bit-identically
+        ck = str(tmp_path / "gated.ck")
+        a.save_state(ck)
+        b.load_state(ck)
+        _same_gate(ga, b.get_row_gate(), "load_state")
+        for t in range(T1, T1 + T2):
+            a.tick(raw=raw[t])
+            b.tick(raw=raw[t])
+        _same_state(a, b, "resumed")
+        _same_gate(a.get_row_gate(), b.get_row_gate(), "resumed")
+        # a gate-less handle's checkpoint loads into a gated one with the gate state zero
+        plain = str(tmp_path / "plain.ck")
+        c.save_state(plain)
+        assert d.get_row_gate()["run"].any()
+        d.load_state(plain)
+        gd = d.get_row_gate()
+        assert not any(gd[k].any() for k in gd)
+        _same_state(c, d, "plain checkpoint")
+        # the gated file is longer by exactly the two sections: the words and the d2 planes
+        assert os.path.getsize(ck) - os.path.getsize(plain) == (8 + 8 * n) + (8 + 24 * n)
+        # a gated checkpoint loads into a gate-less handle, which has no gate state to restore
+        c.load_state(ck)
+        with pytest.raises(fmskf.FmskfError):
+            c.get_row_gate()
+        # reset zeroes the gate state and keeps the configuration
+        a.reset()
+        g0 = a.get_row_gate()
+        assert not any(g0[k].any() for k in g0)
+        bad = raw[T1].copy()
+        bad[:, 0] = np.where(bad[:, 0] < 0, bad[:, 0] + 16384, bad[:, 0] - 16384)  # the yaw off by 90 degrees
+        for t in range(3):  # a fresh filter's heading variance admits anything at first
+            a.tick(raw=raw[t])
+        a.tick(raw=bad)
+        assert np.all(a.get_row_gate()["status"][0] == REJ)  # still gated
+
+
+# ---------------------------------------------------------------------------- 7
+def test_rowgate_config_rules():
+    ENOTSUP, EINVAL = 5, 1
+    cfg = fmskf.default_config("ekf9", 16)
+    r_off = np.array(cfg.r[:21])
+    r_off[5 * 6 // 2 + 4] = 1e-6  # a vbx / vby cross term: the joint update
+    for model, kw in (("rs", {}), ("kf6", {}), ("kf12d", {}), ("ekf9", dict(flags=fmskf.CFG_COMP_POS)),
+                      ("ekf9", dict(r=r_off))):
+        with Engine(model, 16, **kw) as e:
+            with pytest.raises(fmskf.FmskfError) as ei:
+                e.set_row_gate(D2_MAX, 3)
+            assert ei.value.code == ENOTSUP, (model, kw)
+            with pytest.raises(fmskf.FmskfError) as ei:
+                e.set_row_gate(None)
+            assert ei.value.code == ENOTSUP, (model, kw)
+    with Engine("ekf9", 16) as e:
+        with pytest.raises(fmskf.FmskfError) as ei:
+            e.set_gate(18.47, 3)  # the KF6 gate stays a KF6 gate
+        assert ei.value.code == ENOTSUP
+        for bad in (float("nan"), 0.0, -1.0):
+            for row in range(ROWS):
+                d2 = [D2_MAX] * ROWS
+                d2[row] = bad
+                with pytest.raises(fmskf.FmskfError) as ei:
+                    e.set_row_gate(d2, 0)
+                assert ei.value.code == EINVAL, (bad, row)
+        with pytest.raises(fmskf.FmskfError) as ei:
+            e.set_row_gate(D2_MAX, 256)
+        assert ei.value.code == EINVAL
+        import ctypes as C
+        from fmskf import _lib
+        g = _lib.RowGate((C.c_float * 6)(*([D2_MAX] * 6)), 0, 2)  # an unknown flag bit
+        assert fmskf.load().fmskf_set_row_gate(e.h, C.byref(g)) == EINVAL
+        with pytest.raises(fmskf.FmskfError) as ei:
+            e.get_row_gate()  # none of the above set a gate
+        assert ei.value.code == EINVAL
+        e.set_row_gate(float("inf"), 255)
+        g = e.get_row_gate()
+        assert "d2" not in g and not g["status"].any()
+        d2 = np.empty((ROWS, 16), np.float32)  # d2 asked for, the gate set without FMSKF_ROW_GATE_D2
+        assert fmskf.load().fmskf_get_row_gate(e.h, None, None, d2.ctypes.data_as(C.c_void_p), _lib.MEM_HOST) == EINVAL
+        e.set_row_gate(float("inf"), 0, record_d2=True)
+        assert e.get_row_gate()["d2"].shape == (ROWS, 16)

@@ -37,6 +37,11 @@ def main():
     ap.add_argument("--gate", type=float, default=None, metavar="NIS_MAX",
                     help="KF6 with the innovation gate set (fmskf_set_gate; inf: monitor only, nothing rejected)")
     ap.add_argument("--gate-consecutive", type=int, default=0, help="--gate: max_consecutive (0: never force)")
+    ap.add_argument("--row-gate", type=float, default=None, metavar="D2_MAX",
+                    help="EKF9 with the per-row innovation gate set on every row (fmskf_set_row_gate; inf: monitor "
+                         "only); with --outliers the EKF9 recipe (a yaw, a wheel and an ax share per tick, drawn on "
+                         "the device); give a --ring of at least 20 + --ticks as with --gate")
+    ap.add_argument("--row-gate-d2", action="store_true", help="--row-gate: FMSKF_ROW_GATE_D2 (the d2 planes stored)")
     ap.add_argument("--outliers", type=float, default=0.0, metavar="SHARE",
                     help="this share of the robots per tick reads a yaw outlier and the same share again an "
                          "rpm outlier (fmskf.synth.inject_outliers on the input ring; with --gate give a --ring of "
@@ -65,10 +70,13 @@ def main():
     if args.gate is not None:  # + the gate word read and written, the NIS written
         e.set_gate(args.gate, args.gate_consecutive)
         BYTES["kf6"] += 12
+    if args.row_gate is not None:  # + the gate word read and written (+ the six d2 rows written)
+        e.set_row_gate(args.row_gate, args.gate_consecutive, record_d2=args.row_gate_d2)
+        BYTES["ekf9"] += 40 if args.row_gate_d2 else 16
     st = torch.cuda.current_stream()
     e.set_stream(st)
     yaw, gz, rpm = kf6_ring_torch(n, R, device=dev)
-    if args.outliers:
+    if args.outliers and args.model != "ekf9":
         from fmskf.synth import inject_outliers
         oy, orpm, _ = inject_outliers(yaw.cpu().numpy(), rpm.cpu().numpy(), start=0, yaw_share=args.outliers,
                                       rpm_share=args.outliers)
@@ -98,6 +106,19 @@ def main():
         raw = torch.cat([torch.round(yaw / 180.0 * 32768).to(torch.int16)[..., None],
                          torch.round(-gz / 2000.0 * 32768).to(torch.int16)[..., None],
                          torch.zeros(R, n, 2, dtype=torch.int16, device=dev), rpm], -1).contiguous()
+        if args.outliers:  # fmskf.synth.inject_outliers_ekf9's recipe, drawn per tick on the device
+            g = torch.Generator(device=dev)
+            g.manual_seed(0x6A7E)
+            for r in range(R):
+                u = torch.rand(n, generator=g, device=dev)
+                v = raw[r].to(torch.int32)
+                v[:, 0] += torch.where(u < args.outliers, torch.randint(-728, 729, (n,), generator=g, device=dev), 0).int()
+                hit = ((u >= args.outliers) & (u < 2 * args.outliers)).int()
+                wheel = torch.randint(0, 4, (n,), generator=g, device=dev)
+                v[:, 4:].scatter_add_(1, wheel[:, None], (hit * torch.randint(0, 30000, (n,), generator=g, device=dev).int())[:, None])
+                v[:, 2] += torch.where((u >= 2 * args.outliers) & (u < 3 * args.outliers),
+                                       torch.randint(-16000, 16001, (n,), generator=g, device=dev), 0).int()
+                raw[r] = v.clamp(-32768, 32767).to(torch.int16)
         preps = [e.prepare(raw=raw[r]) for r in range(R)]
         many = dict(raw=raw)
     else:
@@ -232,7 +253,7 @@ def main():
     rej0 = int(e.get_gate()["rejects"].sum(dtype=np.int64)) if args.gate is not None else 0
     # gated: the timed ticks go on where the 20 warm-up ticks stopped (a jump back in the
     # trajectory is an outlier for most robots)
-    base = 20 if args.gate is not None else 0
+    base = 20 if args.gate is not None or args.row_gate is not None else 0
     if args.many:
         reps = max(1, args.ticks // args.many)
         sub = {k: v[: args.many] for k, v in many.items()}
@@ -256,6 +277,9 @@ def main():
         done = reps * args.many if args.many else args.ticks
         extra = {"gate": args.gate, "outliers": args.outliers,
                  "rejected_share": (int(e.get_gate()["rejects"].sum(dtype=np.int64)) - rej0) / (n * done)}
+    if args.row_gate is not None:  # the share of the robots' rows the last timed tick rejected
+        extra = {"row_gate": args.row_gate, "d2_planes": args.row_gate_d2, "outliers": args.outliers,
+                 "rejected_rows_last_tick": float((e.get_row_gate()["status"] == fmskf.GATE_REJECTED).mean())}
     if args.ktime and not args.many:  # kernel time alone: HIP events around every launch
         e.set_timing(True)
         for k in range(args.ticks):
