@@ -17,23 +17,30 @@ def pk(i, j):
     return i * (i + 1) // 2 + j if i >= j else j * (j + 1) // 2 + i
 
 
-def params(orc, n, trig=fmskf.TRIG_TABLE512):
+# `prm` (optional, everywhere below): a param_cases.Params of KF6; omitted: fmskf.default_config
+def params(orc, n, trig=fmskf.TRIG_TABLE512, prm=None):
+    otrig = orc.TRIG_LIBM if trig == fmskf.TRIG_LIBM else orc.TRIG_TABLE512
+    if prm is not None:
+        return orc.kf6_params(prm.dt, prm.q, prm.r, otrig)
     cfg = fmskf.default_config("kf6", n)
-    return orc.kf6_params(cfg.dt, np.array(cfg.q[:21]), np.array(cfg.r[:10]),
-                          orc.TRIG_LIBM if trig == fmskf.TRIG_LIBM else orc.TRIG_TABLE512)
+    return orc.kf6_params(cfg.dt, np.array(cfg.q[:21]), np.array(cfg.r[:10]), otrig)
 
 
-def r_packed(n=1):
+def r_packed(n=1, prm=None):
     """the filter's R: the fp32 values the kernels receive"""
+    if prm is not None:
+        return np.float32(prm.r).astype(np.float64)
     return np.float32(np.array(fmskf.default_config("kf6", n).r[:10])).astype(np.float64)
 
 
-def fresh(n):
+def fresh(n, prm=None):
+    if prm is not None:
+        return np.zeros((6, n), np.float32), np.repeat(np.float32(prm.p0)[:, None], n, 1).copy()
     cfg = fmskf.default_config("kf6", n)
     return np.zeros((6, n), np.float32), np.repeat(np.float32(np.array(cfg.p0[:21]))[:, None], n, 1).copy()
 
 
-def nis_f64(orc, x, P, yaw, gz, rpm, trig=fmskf.TRIG_TABLE512):
+def nis_f64(orc, x, P, yaw, gz, rpm, trig=fmskf.TRIG_TABLE512, prm=None):
     """NIS [n] in float64 of the measurement (yaw, gz, rpm) against the fp32 state (x, P)"""
     z = orc.kf6_measure(np.ascontiguousarray(yaw, np.float32), np.ascontiguousarray(gz, np.float32),
                         np.ascontiguousarray(rpm, np.int16),
@@ -43,7 +50,7 @@ def nis_f64(orc, x, P, yaw, gz, rpm, trig=fmskf.TRIG_TABLE512):
     y = z - x[list(H)]
     y[0] = np.where(y[0] > np.pi, y[0] - 2 * np.pi, np.where(y[0] < -np.pi, y[0] + 2 * np.pi, y[0]))
     n = x.shape[1]
-    R = r_packed()
+    R = r_packed(prm=prm)
     S = np.empty((n, 4, 4))
     for a in range(4):
         for b in range(4):

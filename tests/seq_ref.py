@@ -192,12 +192,20 @@ class Fleet:
     that read the ingested page, half the fleet powered, one target); `apply(op)` advances by one
     op and returns the 0x200 frames the op produced (None where it produced none)."""
 
-    def __init__(self, orc, model, n, inp):
+    def __init__(self, orc, model, n, inp, prm=None):
+        """prm (optional): a param_cases.Params -- dt, Q, R, P0 of the estimator and the motor
+        directions; omitted: fmskf.default_config"""
         self.orc, self.model, self.n, self.inp = orc, model, n, inp
         self.cprm = [orc.ctrl_params(**kw) for kw in _ORC_PARAMS]
         self.pidx = 0
+        self.dirs = (1, 1, -1, -1) if prm is None else tuple(prm.motor_dir)
         cfg = fmskf.default_config(model, n)
-        if model == "kf6":
+        if prm is not None and model in ("kf6", "ekf9"):
+            assert prm.model == model
+            mk = orc.kf6_params if model == "kf6" else orc.ekf9_params
+            self.prm = mk(prm.dt, prm.q, prm.r, orc.TRIG_TABLE512)
+            self.p0 = np.float32(prm.p0)
+        elif model == "kf6":
             self.prm = orc.kf6_params(cfg.dt, np.array(cfg.q[:21]), np.array(cfg.r[:10]), orc.TRIG_TABLE512)
             self.p0 = np.float32(np.array(cfg.p0[:21]))
         elif model == "ekf9":
@@ -210,8 +218,8 @@ class Fleet:
 
     def _zero(self):
         orc, n = self.orc, self.n
-        self.mb = orc.MotorBatch(n)
-        self.ref = orc.CtrlBatch(n, self.cprm[self.pidx])
+        self.mb = orc.MotorBatch(n, self.dirs)
+        self.ref = orc.CtrlBatch(n, self.cprm[self.pidx], motor_dir=self.dirs)
         self.wb = orc.Wt901Batch(n) if self.model != "ekf9" else None
         if self.model == "rs":
             self.pos, self.vel = np.zeros((3, n), np.float32), np.zeros((3, n), np.float32)

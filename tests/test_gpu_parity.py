@@ -134,11 +134,17 @@ def _kf6_setup(n, T, seed):
     return tr, yaw, gz, rpm, valid
 
 
-def _kf6_oracle(orc, n, yaw, gz, rpm, valid, trig, ticks):
+def _kf6_oracle(orc, n, yaw, gz, rpm, valid, trig, ticks, params=None):
+    """params (optional): a param_cases.Params of KF6; omitted: fmskf.default_config"""
     cfg = fmskf.default_config("kf6", n)
-    prm = orc.kf6_params(cfg.dt, np.array(cfg.q[:21]), np.array(cfg.r[:10]), trig)
+    if params is not None:
+        prm = orc.kf6_params(params.dt, params.q, params.r, trig)
+        p0 = np.float32(params.p0)
+    else:
+        prm = orc.kf6_params(cfg.dt, np.array(cfg.q[:21]), np.array(cfg.r[:10]), trig)
+        p0 = np.float32(np.array(cfg.p0[:21]))
     x = np.zeros((6, n), np.float32)
-    P = np.repeat(np.float32(np.array(cfg.p0[:21]))[:, None], n, 1).copy()
+    P = np.repeat(p0[:, None], n, 1).copy()
     for t in range(ticks):
         orc.kf6_tick(x, P, yaw[t], gz[t], rpm[t], None if valid is None else valid[t], prm,
                      nthreads=0)
