@@ -136,7 +136,13 @@ int fmskf_model_dims(uint32_t model, uint32_t *n, uint32_t *m, uint32_t *elem_by
  * IMU_IF_WT901C::update (imu_if_wt901c.cpp:83-89): is_error = no quaternion frame
  * since the last good poll; else refresh the Data page (updateData, :91-129).
  * bytes: instance i's bytes at bytes + i*stride, len[i] <= stride.
- * latch_qinit != 0 additionally latches q_init after a good poll (init(), :70-76). */
+ * latch_qinit != 0 makes the poll init() (:63-76): WitInit first empties the parser window
+ * (wit_c_sdk.c:355-362: the head of a frame split across the poll before is dropped), the
+ * bytes are parsed, and after a good poll the page is refreshed and q_init latched; init()'s
+ * getDataImmediately (:149-158) does not write is_error, so after a good latching poll the
+ * flag keeps the last update()'s answer.  (init() also re-reads register q0; the handle's
+ * imu_read_reg is configuration and a latch leaves it, which is the firmware's behaviour at
+ * the default 0x51.) */
 int fmskf_ingest_wt901(fmskf_handle h, const uint8_t *bytes, uint32_t stride, const uint32_t *len,
                        int latch_qinit, uint32_t mem);
 

@@ -288,10 +288,18 @@ void orc_wt901_update_data(orc_wt901 *s) {
   d[15] = (qi[0] * q[0] + qi[1] * q[1] + qi[2] * q[2] + qi[3] * q[3]);
 }
 
-/* IMU_IF_WT901C::update, imu_if_wt901c.cpp:83-89; q_init latch per init(), :70-76 */
+/* IMU_IF_WT901C::update, imu_if_wt901c.cpp:83-89; q_init latch per init(), :70-76.  A
+ * latching poll that holds its quaternion frame is init() -> getDataImmediately (:149-158):
+ * isComComp, updateData, the latch, and is_error is NOT written (the reference's own build
+ * keeps the last update()'s flag there: tests/golden/imu_ref.npz).  A latching poll without
+ * one has no firmware counterpart (init() spins); it stays a failed update().  init() begins
+ * with WitInit (wit_c_sdk.c:355-362), which empties the parser window (s_uiWitDataCnt = 0):
+ * the bytes of a frame split across the poll before are dropped. */
 void orc_wt901_update(orc_wt901 *s, const uint8_t *bytes, uint32_t len, int latch_qinit) {
-  s->is_error = !orc_wt901_is_com_comp(s, bytes, len);
-  if (!s->is_error) {
+  if (latch_qinit) s->cnt = 0;
+  const int ok = orc_wt901_is_com_comp(s, bytes, len);
+  if (!(ok && latch_qinit)) s->is_error = !ok;
+  if (ok) {
     orc_wt901_update_data(s);
     if (latch_qinit)
       for (int i = 0; i < 4; i++) s->q_init[i] = s->reg[R_Q0 + i] / 32768.0f;

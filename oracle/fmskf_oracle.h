@@ -11,15 +11,19 @@
  *   - WT901 byte parser + register file (A1, A2): PINNED against oracle/_ref,
  *     the reference's own lib/wt901c/wit_c_sdk.c compiled here, via the golden
  *     fixtures in tests/golden/wt901_*.npz.
- *   - IMU conversion (A3, A4), CAN unwrap (A8), odometry integrator (A9-A12):
- *     restated from the reference source; the reference files need Arduino /
- *     CMSIS-DSP / FreeRTOS headers absent from this image, so they are
- *     unbuildable here -> pinned only by known-answer tests derived from the
- *     reference constants (tests/test_oracle_known_answers.py).  Parity
- *     against the reference binary itself is UNPINNED for these rows.
+ *   - IMU conversion (A3, A4), CAN unwrap (A8), odometry integrator (A9-A12, A14),
+ *     velocity interpolator and current narrowing: restated from the reference
+ *     source and PINNED against the reference's own VD_vehicle_controller.cpp,
+ *     VD_motor_if_m2006.cpp, util_vel_interp.hpp, util_mymath.hpp and
+ *     imu_if_wt901c.cpp, compiled here against stand-in headers for Arduino /
+ *     CMSIS-DSP / the RTOS (oracle/ref_standin), via tests/golden/vehicle_ref.npz
+ *     and imu_ref.npz.  The cases an x86 build cannot show (x/0, VCVT saturation,
+ *     a latch without a quaternion frame) keep their known answers
+ *     (tests/test_oracle_known_answers.py).
  *   - CMSIS-DSP arm_sin_f32 / arm_cos_f32 (A13, third-party, absent): restated
  *     from the published CMSIS-DSP 5.x algorithm (512-entry table + linear
- *     interpolation).  UNPINNED against the device library.
+ *     interpolation).  UNPINNED against the device library: the stand-in
+ *     arm_math.h forwards to this restatement.
  *   - KF / EKF math (A15): no reference counterpart (new math defined by the
  *     north star).  The fp32 restatement here is checked against an
  *     independent fp64 dense restatement (oracle/kf_ref.py).
@@ -70,8 +74,10 @@ void orc_wt901_reset(orc_wt901 *s, uint32_t read_reg_index);
 void orc_wt901_byte(orc_wt901 *s, uint8_t b);                 /* WitSerialDataIn */
 int  orc_wt901_is_com_comp(orc_wt901 *s, const uint8_t *bytes, uint32_t len); /* isComComp */
 void orc_wt901_update_data(orc_wt901 *s);                     /* updateData */
-/* IMU_IF_WT901C::update() on one poll's bytes; latch_qinit emulates init()'s
- * q_init latch (imu_if_wt901c.cpp:70-76) after a successful poll. */
+/* IMU_IF_WT901C::update() on one poll's bytes; latch_qinit makes it init()
+ * (imu_if_wt901c.cpp:63-76): WitInit empties the parser window first, q_init is
+ * latched after a successful poll, and such a poll leaves is_error as it was.
+ * read_reg_index stays (init() re-reads q0 = 0x51, the default). */
 void orc_wt901_update(orc_wt901 *s, const uint8_t *bytes, uint32_t len, int latch_qinit);
 /* batched: bytes[i*stride ...], len[i] */
 void orc_wt901_update_batch(size_t n, orc_wt901 *s, const uint8_t *bytes, uint32_t stride,

@@ -1,5 +1,5 @@
-"""ctypes bindings for the oracle (liboracle.so) and the reference WT901 SDK build
-(_ref/libwit_ref.so).
+"""ctypes bindings for the oracle (liboracle.so) and the builds of the reference's own files
+(_ref/libwit_ref.so, libctrl_ref.so, libvehicle_ref.so, libimu_ref.so).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py, never by the product package.
@@ -16,6 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
 REF_PATH = os.path.join(HERE, "_ref", "libwit_ref.so")
 REF_CTRL_PATH = os.path.join(HERE, "_ref", "libctrl_ref.so")
+REF_VEHICLE_PATH = os.path.join(HERE, "_ref", "libvehicle_ref.so")
+REF_IMU_PATH = os.path.join(HERE, "_ref", "libimu_ref.so")
 
 TRIG_TABLE512 = 0
 TRIG_LIBM = 1
@@ -390,13 +392,17 @@ class MotorBatch:
             for w in range(4):
                 lib().orc_m2006_reset(C.byref(self.m[4 * i + w]), int(dirs[w]))
 
-    def rx(self, frames, stamps):
-        """frames [n][4][8] uint8, stamps [n][4] int16, every wheel present"""
+    def rx(self, frames, stamps, present=None):
+        """frames [n][4][8] uint8, stamps [n][4] int16; present [n] uint8, bit w = wheel w has a
+        frame (None: every wheel present)"""
         frames = np.ascontiguousarray(frames, np.uint8)
         stamps = np.ascontiguousarray(stamps, np.int16)
         assert frames.shape == (self.n, 4, 8) and stamps.shape == (self.n, 4)
+        if present is not None:
+            present = np.ascontiguousarray(present, np.uint8)
+            assert present.shape == (self.n,)
         lib().orc_can_ingest_batch(self.n, C.cast(self.m, C.c_void_p), frames.ctypes.data_as(C.c_void_p),
-                                   stamps.ctypes.data_as(C.c_void_p), None)
+                                   stamps.ctypes.data_as(C.c_void_p), _ptr(present))
 
     def field(self, name):
         """[n][4] of one M2006 field"""
@@ -709,3 +715,112 @@ class RefFfPiD:
         cls.lib().ref_ffpid_run(c_freq, ff, pg, ig, dg, ilim, lpf, fflim, n, tgt, val, _ptr(rs),
                                 ctrl, now_val, target)
         return ctrl, now_val, target
+
+
+# ----------------------------------------------------------------------------- reference VEHICLE_CTRL
+class RefVehicle:
+    """The reference's own VEHICLE_CTRL with four MOTOR_IF_M2006, four FF_PI_D and three
+    VelInterpConstJerk (oracle/ref_vehicle_harness.cpp, compiled from /root/reference against the
+    stand-in headers of oracle/ref_standin into oracle/_ref/libvehicle_ref.so; its arm_sin_f32 /
+    arm_cos_f32 are the oracle's own table restatement).  Only where the reference existed at
+    build time; the fixtures it produced are committed under tests/golden/.  Keyword arguments
+    as ctrl_params()."""
+
+    _l = None
+
+    @classmethod
+    def lib(cls):
+        if cls._l is None:
+            if not os.path.exists(REF_VEHICLE_PATH):
+                raise FileNotFoundError(REF_VEHICLE_PATH)
+            lib()  # liboracle.so (orc_sin / orc_cos) exists before the harness resolves it
+            L = C.CDLL(REF_VEHICLE_PATH)
+            L.ref_vehicle_new.restype = C.c_void_p
+            L.ref_vehicle_new.argtypes = [C.c_char_p] + [C.c_float] * 9 + [C.c_int16]
+            L.ref_vehicle_free.argtypes = [C.c_void_p]
+            L.ref_vehicle_rx.argtypes = [C.c_void_p, C.c_int, _u8p, C.c_int16]
+            L.ref_vehicle_power.argtypes = [C.c_void_p, C.c_int]
+            L.ref_vehicle_set_target_vel.argtypes = [C.c_void_p, _f32p, _f32p, _f32p]
+            L.ref_vehicle_tick.argtypes = [C.c_void_p, C.c_float]
+            L.ref_vehicle_read.argtypes = [C.c_void_p, _f32p, _f32p, _f32p, _i16p, _i64p, _i16p, _f32p]
+            cls._l = L
+        return cls._l
+
+    def __init__(self, motor_dir=(1, 1, -1, -1), **kw):
+        a = dict(CTRL_DEFAULTS)
+        a.update(kw)
+        d = np.asarray(motor_dir, np.int8).tobytes()
+        self.h = self.lib().ref_vehicle_new(d, a["c_freq"], a["ff"], a["pg"], a["ig"], a["dg"], a["ilim"],
+                                            a["lpf"], a["fflim"], float(a["ts"]), int(a["clim"]))
+
+    def close(self):
+        if self.h:
+            self.lib().ref_vehicle_free(self.h)
+            self.h = None
+
+    def rx(self, wheel, frame, stamp):
+        f = np.ascontiguousarray(frame, np.uint8)
+        self.lib().ref_vehicle_rx(self.h, int(wheel), f, int(np.int16(stamp)))
+
+    def power(self, on):
+        self.lib().ref_vehicle_power(self.h, int(bool(on)))
+
+    def set_target_vel(self, vel, acl, jrk):
+        v, a, j = (np.ascontiguousarray(x, np.float32) for x in (vel, acl, jrk))
+        self.lib().ref_vehicle_set_target_vel(self.h, v, a, j)
+
+    def tick(self, yaw_deg):
+        self.lib().ref_vehicle_tick(self.h, float(np.float32(yaw_deg)))
+
+    def read(self):
+        """dict of pose [3], vel [3], vel_tgt [3] float32, curr [4] int16 (get_rawCurr_tgt),
+        angle_sum [4] int64, st_i16 [4][4] (microsec_id, rawAngle, rawSpeedRpm, rawCurr) and
+        st_f32 [4][2] (dltOutAngle_rad, SpeedRadPS) of get_status_latest"""
+        o = dict(pose=np.zeros(3, np.float32), vel=np.zeros(3, np.float32), vel_tgt=np.zeros(3, np.float32),
+                 curr=np.zeros(4, np.int16), angle_sum=np.zeros(4, np.int64),
+                 st_i16=np.zeros((4, 4), np.int16), st_f32=np.zeros((4, 2), np.float32))
+        self.lib().ref_vehicle_read(self.h, *o.values())
+        return o
+
+
+# ----------------------------------------------------------------------------- reference IMU_IF_WT901C
+class RefImu:
+    """The reference's own IMT::IMU_IF_WT901C on a byte-queue serial port
+    (oracle/ref_imu_harness.cpp -> oracle/_ref/libimu_ref.so).  The interface and the SDK keep
+    file-static state: one process, one stream.  Only where the reference existed at build time."""
+
+    _l = None
+
+    def __init__(self):
+        if RefImu._l is None:
+            if not os.path.exists(REF_IMU_PATH):
+                raise FileNotFoundError(REF_IMU_PATH)
+            L = C.CDLL(REF_IMU_PATH)
+            L.ref_imu_init.argtypes = [_u8p, C.c_uint32]
+            L.ref_imu_init.restype = C.c_int
+            L.ref_imu_poll.argtypes = [_u8p, C.c_uint32]
+            L.ref_imu_read.argtypes = [_f32p]
+            L.ref_imu_read.restype = C.c_int
+            RefImu._l = L
+        else:
+            raise RuntimeError("RefImu: the reference keeps static state, one instance per process")
+
+    @staticmethod
+    def _bytes(data):
+        b = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else data
+        b = np.ascontiguousarray(b, np.uint8)
+        return (b, b.size) if b.size else (np.zeros(1, np.uint8), 0)
+
+    def init(self, data):
+        """IMU_IF_WT901C::init() answered by `data`; raises when they hold no quaternion frame"""
+        if RefImu._l.ref_imu_init(*self._bytes(data)) != 0:
+            raise RuntimeError("init(): the queued bytes held no quaternion frame")
+
+    def poll(self, data):
+        RefImu._l.ref_imu_poll(*self._bytes(data))
+
+    def read(self):
+        """(Data page [16] float32, is_error)"""
+        d = np.zeros(16, np.float32)
+        err = RefImu._l.ref_imu_read(d)
+        return d, bool(err)

@@ -217,7 +217,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FMSKF_WT
   // Every unconditional load first -- the count, flags, length and the poll row -- so a wave
   // waits for memory once before parsing (the parser words, read only when bytes are pending, and
   // a non-standard poll's register reads come after)
-  const uint32_t cnt_in = a.cnt[i];
+  const uint32_t cnt_mem = a.cnt[i];
+  // a poll that latches q_init is init(), which begins with WitInit (wit_c_sdk.c:355-362:
+  // s_uiWitDataCnt = 0): bytes of a frame still pending in the parser window are dropped
+  const uint32_t cnt_in = a.latch_qinit ? 0u : cnt_mem;
   const uint32_t flags_in = a.flags[i];
   const uint32_t len_in = a.len[i];
   int16_t *reg = a.reg;
@@ -338,7 +341,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FMSKF_WT
   // isComComp / update, imu_if_wt901c.cpp:83-89,132-143
   const bool ok = (flags & F_QUAT) != 0;
   if (ok) flags = 0;
-  a.err[i] = ok ? 0 : 1;
+  // a poll that latches q_init is init() (getDataImmediately, :149-158), which does not write
+  // is_error: once it has its quaternion frame the flag keeps the last update()'s answer
+  if (!(ok && a.latch_qinit)) a.err[i] = ok ? 0 : 1;
   // the standard poll (always a successful one) leaves its row-resident registers in the row
   if (std4) flags |= F_ROWREGS;
   // a successful poll's snapshot takes the magnetometer registers as they are (F_MAGDET clear);
@@ -353,7 +358,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FMSKF_WT
       flags |= F_MAGDET;
     }
   }
-  if (cnt_in != 0 || cnt != 0) {
+  if (cnt_mem != 0 || cnt != 0) {  // (a window dropped by a latch is written back empty: all zero)
     a.parser[i] = (uint32_t)lo;
     a.parser[n + i] = (uint32_t)(lo >> 32);
     a.parser[2 * n + i] = (uint32_t)hi;

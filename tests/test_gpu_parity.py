@@ -567,16 +567,24 @@ def test_wt901_data_page_across_latches(orc, stride):
     snapshot row only (round 6), and a failed poll, a 0x5F register reply (Q0-Q3) or another
     frame mix after it must see them (wit_c_sdk.c:90-130).  And the tick's yaw: an RS handle fed
     the same polls takes Data.angle[2] from the Yaw / GZ words (round 6) in its correct step
-    (theta = deg2rad(yaw), VD_task_main.cpp:368), so theta follows the page, not the register."""
+    (theta = deg2rad(yaw), VD_task_main.cpp:368), so theta follows the page, not the register.
+    A latching poll is the firmware's init() (getDataImmediately, imu_if_wt901c.cpp:149-158),
+    which does not write is_error: a robot whose latching poll holds its quaternion frame keeps
+    the flag of its last update(), set or clear (the reference's own build: tests/golden/
+    imu_ref.npz); checked here on the flags themselves as well as against the oracle.  It also
+    begins with WitInit, which empties the parser window; these polls are whole frames, so the
+    window is empty at every latch (the fixture tests hold the split-frame case)."""
     n, polls = 1537, 9
     rng = np.random.default_rng(41 + stride)
     orcs = [orc.Wt901(0x51) for _ in range(n)]
     latch = {1, 5}
     deg2rad = np.float32(np.float32(3.14159265358979) / np.float32(180.0))  # util_mymath.hpp:14
+    prev_err, kept_set = np.zeros(n, np.uint8), 0
     with Engine("kf6", n) as e, Engine("rs", n) as rs:
         for k in range(polls):
             buf = np.zeros((n, stride), np.uint8)
             lens = np.zeros(n, np.uint32)
+            quat = np.zeros(n, bool)  # the poll completes: a quaternion frame or the Q0-Q3 reply
             for i in range(n):
                 r = rng.random()
                 if k == 0 and i % 3:  # most robots have no successful poll before the first latch
@@ -594,6 +602,7 @@ def test_wt901_data_page_across_latches(orc, stride):
                 b = np.frombuffer(b"".join(wt901_frame(t, rng.integers(0, 65536, 4)) for t in ts), np.uint8)
                 buf[i, :b.size] = b
                 lens[i] = b.size
+                quat[i] = 0x59 in ts or 0x5F in ts
                 orcs[i].update(b, latch_qinit=(k in latch))
             e.ingest_wt901(buf, lens, latch_qinit=(k in latch))
             rs.ingest_wt901(buf, lens, latch_qinit=(k in latch))
@@ -603,6 +612,11 @@ def test_wt901_data_page_across_latches(orc, stride):
             for i in range(n):
                 assert err[i] == orcs[i].is_error
                 bits_equal(data[:, i], orcs[i].data, f"data {i} poll {k}")
+            # update(): is_error = no quaternion frame; init(): the flag stays
+            want_err = np.where(quat & (k in latch), prev_err, (~quat).astype(np.uint8))
+            np.testing.assert_array_equal(err, want_err, err_msg=f"is_error poll {k}")
+            kept_set += int((quat & (prev_err == 1)).sum()) if k in latch else 0
+            prev_err = err.copy()
             yaw = np.array([orcs[i].data[11] for i in range(n)], np.float32)
             bits_equal(th, yaw * deg2rad, f"theta poll {k}")
             if k % 3 == 1:  # the register file (round 6: the standard poll keeps eleven of its
@@ -612,6 +626,7 @@ def test_wt901_data_page_across_latches(orc, stride):
                 for i in range(0, n, 3):
                     np.testing.assert_array_equal(regs[:, i], orcs[i].regs, err_msg=f"regs {i} poll {k}")
         vi = e.export_vehicle_info()
+    assert kept_set > 50, kept_set  # latches after a failed poll happened
     for i in range(0, n, 5):
         d = orcs[i].data
         if orcs[i].is_error:

@@ -3,11 +3,16 @@ VehicleInfo export.
 
 * FF_PI_D (util_controller.hpp) is pinned bit for bit by tests/golden/ctrl_ref.npz, made
   by tests/golden/make_golden_ctrl.py from the reference's own header compiled here.
-* VelInterpConstJerk (util_vel_interp.hpp) includes arm_math.h (CMSIS-DSP, absent): it is
-  pinned by known answers derived from its own formulas (profile durations, the reached
-  velocity, the no-constant-acceleration branch); arm_sqrt_f32 is parity unpinned.
+* VelInterpConstJerk (util_vel_interp.hpp) includes arm_math.h (CMSIS-DSP, absent).  Here it
+  is held by known answers derived from its own formulas (profile durations, the reached
+  velocity, the no-constant-acceleration branch); the reference's own header, compiled against
+  a stand-in arm_math.h inside VEHICLE_CTRL, pins it bit for bit in tests/golden/
+  vehicle_ref.npz (tests/test_vehicle_golden_cpu.py).  The stand-in's arm_sqrt_f32 is the
+  correctly rounded square root for inputs >= 0 and 0 otherwise, as VSQRT.F32 is: that much
+  of CMSIS-DSP is taken from its documentation, not from its code.
 * The integer conversions follow Cortex-M7 semantics (VCVT saturates, NaN -> 0, the int16
-  narrowing keeps the low 16 bits) and are pinned by hand-derived known answers.
+  narrowing keeps the low 16 bits) and are pinned by hand-derived known answers; the int16
+  narrowing of in-range currents (32768 .. 2^31 raw) is in vehicle_ref.npz too.
 """
 import ctypes as C
 import os
