@@ -160,9 +160,9 @@ struct Kf6Params {
 };
 constexpr uint32_t kKf6LoRows = 5;
 // The chi-square innovation gate of a KF6 handle (fmskf_set_gate): its configuration and the
-// per-robot gate state, two plain [N] planes read and written by the gated tick kernels alone
-// (kernels_gate.hip; they take it in an argument struct of their own, GateArgs, so the ungated
-// kernels' arguments do not move).  word: bits 0-1 the status (FMSKF_GATE_*), bits 2-9 the run
+// per-robot gate state, two plain [N] planes read and written by the gated instantiations of the
+// tick kernels alone (kernels_kf6.hip; they take it in an argument struct of their own, kf6_lane.hpp
+// GateArgs, so the ungated kernels' arguments do not move).  word: bits 0-1 the status (FMSKF_GATE_*), bits 2-9 the run
 // of consecutive rejections, bits 10-31 the total rejections, both saturating; nis: the last
 // evaluated normalized innovation squared.
 struct GateDev {
@@ -173,8 +173,8 @@ struct GateDev {
 };
 constexpr uint32_t kGateRunShift = 2, kGateRunMax = 255, kGateRejShift = 10, kGateRejMax = (1u << 22) - 1u;
 // The per-row innovation gate of an EKF9 handle (fmskf_set_row_gate): its configuration and the
-// per-robot state, read and written by the row-gated tick kernels alone (kernels_rowgate.hip; an
-// argument struct of their own, RowGateArgs).  word [N]: bits 0-11 the six rows' 2-bit statuses,
+// per-robot state, read and written by the row-gated instantiations of the tick kernels alone
+// (kernels_kf.hip; an argument struct of their own, ekf9_lane.hpp RowGateArgs).  word [N]: bits 0-11 the six rows' 2-bit statuses,
 // bits 12-59 their 8-bit runs (kf_generic.hpp kRowGate*); d2 [6][d2_pitch]: every row's last
 // evaluated normalised innovation squared, stored only with FMSKF_ROW_GATE_D2.
 struct RowGateDev {
@@ -410,7 +410,7 @@ int launch_rs(const DevState &s, const TickIn &in, bool libm, bool correct, bool
 // in.ens_blocks set (upd and pred only): *ens_nb receives the grid, i.e. the record count
 int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, bool upd,
                bool pred, hipStream_t st, int *ens_nb = nullptr);
-// the gated KF6 measurement update (kernels_gate.hip), with the predict (pred) or alone; plain
+// the gated KF6 measurement update (kernels_kf6.hip), with the predict (pred) or alone; plain
 // state only (no FMSKF_CFG_COMP_POS), no fused ensemble record
 int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,
                     bool pred, hipStream_t st);
@@ -422,7 +422,7 @@ int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_
 int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st);
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
                 bool pred, hipStream_t st, int *ens_nb = nullptr);
-// the row-gated EKF9 measurement update (kernels_rowgate.hip), with the predict (pred) or alone;
+// the row-gated EKF9 measurement update (kernels_kf.hip), with the predict (pred) or alone;
 // tiled plain state (no FMSKF_CFG_COMP_POS), diagonal R, no fused ensemble record
 int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p, const RowGateDev &g,
                         bool libm, bool pred, hipStream_t st);

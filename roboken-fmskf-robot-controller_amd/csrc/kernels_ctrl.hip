@@ -183,7 +183,8 @@ __global__ __launch_bounds__(kBlock) void k_isr_kf6(KfArgs<MdKF6, Kf6Params> a, 
   Kf6Lo<O> lo;  // O::COMP: the position low parts (FMSKF_CFG_COMP_POS)
   kf6_load_lo<O>(a.prm.lo, ic, lo);
   if constexpr (CAN) m.rpm = cl.step(can, live);  // the rpm this tick's frames carried
-  kf6_tick1<O>(m, stab, a.prm, x, P, lo);
+  Kf6Gate<O, false> gt;  // no gated form: the gated handle takes the three-kernel ISR
+  kf6_tick1<O>(m, stab, a.prm, x, P, lo, gt);
   if (live) {
     kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
     kf6_store_lo<O>(a.prm.lo, i, lo);

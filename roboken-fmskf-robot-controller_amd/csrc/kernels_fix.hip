@@ -7,7 +7,7 @@
 // predict, and no robot that is not listed is read or written.
 //
 // The update is the tick's, instantiated for another H: kf_update_factor, NIS from w and D^-1 as
-// the chi-square gate forms it (kernels_gate.hip), then kf_update_apply behind the per-lane
+// the chi-square gate forms it (kf_nis), then kf_update_apply behind the per-lane
 // decision -- with the EKF9's compensated heading (CI = 2, th_add / th_norm) and, for KF6 with
 // FMSKF_CFG_COMP_POS, the position low parts (CXM / CPM) exactly where the models' own updates
 // have them.  A rejected or ignored lane stores nothing.
@@ -129,9 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_fix(FixArgs a) {
     y[1] = COMP ? (z[1] - x[1]) - cl[1] : z[1] - x[1];
     if constexpr (MM == 3) y[2] = EKF ? wrap_innov((z[2] - x[2]) - lo) : wrap_innov(z[2] - x[2]);
     kf_update_factor<Md, float, NX, MM, NP>(P, y, a.r, U, dinv, w);
-    nis = w[0] * (w[0] * dinv[0]);
-#pragma unroll
-    for (int b = 1; b < MM; b++) nis = dfma(w[b], w[b] * dinv[b], nis);
+    nis = kf_nis(w, dinv);
     const bool apply = nis <= a.nis_max;  // a NaN NIS never applies
     status = apply ? FMSKF_GATE_ACCEPTED : FMSKF_GATE_REJECTED;
     if (apply) {

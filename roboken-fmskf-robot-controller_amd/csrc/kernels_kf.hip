@@ -7,6 +7,9 @@
 // F / H / Q / R are shared: H and the sparsity of F are compile-time model traits
 // (kf_generic.hpp), Q / R / dt ride in the kernarg segment (scalar loads, SGPRs).
 // The 6-state headline kernel lives in kernels_kf6.hip.
+// The EKF9 per-row innovation gate (fmskf_set_row_gate) is an instantiation of the EKF9 tick
+// kernels on RowGateArgs (ekf9_lane.hpp): one more lane struct loaded with the state and stored
+// with it, the gated sequential update inside ekf9_tick1, the plain handle's launch regimes.
 #include "can_lane.hpp"
 #include "ctrl_lane.hpp"
 #include "ekf9_lane.hpp"
@@ -37,10 +40,14 @@ struct Ekf9Lo {
 };
 
 // tick_many: T ticks per launch, state in VGPRs; the next tick's raw record (16 B) and validity
-// byte are loaded while the current tick computes (ping-pong registers, loop unrolled by two)
-template <bool LIBM, bool UPD, bool PRED, bool SEQ, bool COMP = false>
-__global__ __launch_bounds__(kBlock) void k_ekf9(KfArgs<MdEKF9, Ekf9Params> a) {
+// byte are loaded while the current tick computes (ping-pong registers, loop unrolled by two).
+// A: Ekf9Args, or RowGateArgs for a row-gated handle (every tick kernel here): the lane's gate
+// state is loaded with the other loads and stored with the state, the gate word held across the
+// ticks.
+template <bool LIBM, bool UPD, bool PRED, bool SEQ, bool COMP = false, class A = Ekf9Args>
+__global__ __launch_bounds__(kBlock) void k_ekf9(A aa) {
   constexpr int N = 9, NP = 45;
+  const Ekf9Args &a = kf_args(aa);
   __shared__ float stab[LIBM ? 1 : 513];
   if (!LIBM) {
     for (int k = threadIdx.x; k < 513; k += kBlock) stab[k] = a.in.sintab[k];
@@ -75,6 +82,8 @@ __global__ __launch_bounds__(kBlock) void k_ekf9(KfArgs<MdEKF9, Ekf9Params> a) {
   float lo = a.prm.thlo[ic];
   Ekf9Lo<COMP, 0> cl;
   cl.load(a.prm.clo, blockIdx.x, tile_slot(n));
+  Ekf9GateOf<A, 0> gt;
+  gt.load(gate_dev(aa), (uint64_t)blockIdx.x * kBlock, n, tile_slot(n));
   uint4 ra = raw_at(0), rb;
   bool ha = have_at(0), hb;
   for (uint32_t t = 0; t < T; t += 2) {
@@ -82,17 +91,18 @@ __global__ __launch_bounds__(kBlock) void k_ekf9(KfArgs<MdEKF9, Ekf9Params> a) {
       rb = raw_at(t + 1);
       hb = have_at(t + 1);
     }
-    ekf9_tick1<LIBM, UPD, PRED, SEQ, COMP>(a, ra, ha, stab, x, P, lo, cl.v);
+    ekf9_tick1<LIBM, UPD, PRED, SEQ, COMP>(aa, ra, ha, stab, x, P, lo, cl.v, gt);
     if (t + 1 >= T) break;
     if (t + 2 < T) {
       ra = raw_at(t + 2);
       ha = have_at(t + 2);
     }
-    ekf9_tick1<LIBM, UPD, PRED, SEQ, COMP>(a, rb, hb, stab, x, P, lo, cl.v);
+    ekf9_tick1<LIBM, UPD, PRED, SEQ, COMP>(aa, rb, hb, stab, x, P, lo, cl.v, gt);
   }
   if (live) {
     a.prm.thlo[i] = lo;
     cl.store(a.prm.clo, blockIdx.x, tile_slot(n));
+    gt.store(gate_dev(aa), (uint64_t)blockIdx.x * kBlock, n, tile_slot(n));
     if constexpr (FMSKF_TILED) {
 #pragma unroll
       for (int k = 0; k < N; k++) tx.st(k, x[k]);
@@ -111,9 +121,12 @@ __global__ __launch_bounds__(kBlock) void k_ekf9(KfArgs<MdEKF9, Ekf9Params> a) {
 // Single tick, straight line (as k_kf6t): no tick loop, clamped index for lanes past N (only
 // their stores and NaN count are masked), every load issued before the table barrier.
 // ENS: the record epilogue of fmskf_tick_ensemble (ens_device.hpp)
-template <bool LIBM, bool UPD, bool PRED, bool SEQ, int CP = 0, bool ENS = false, bool COMP = false>
-__global__ __launch_bounds__(kBlock) void k_ekf9t(KfArgs<MdEKF9, Ekf9Params> a) {
+template <bool LIBM, bool UPD, bool PRED, bool SEQ, int CP = 0, bool ENS = false, bool COMP = false,
+          class A = Ekf9Args>
+__global__ __launch_bounds__(kBlock) void k_ekf9t(A aa) {
   constexpr int N = 9, NP = 45;
+  static_assert(!ENS || std::is_same<A, Ekf9Args>::value, "no fused ensemble record with the row gate");
+  const Ekf9Args &a = kf_args(aa);
   uint32_t bid = blockIdx.x;  // the tick block (the carried fold blocks come first)
   if constexpr (ENS) {
     if (ens_fold_front<9>(a.in, bid)) return;
@@ -146,11 +159,14 @@ __global__ __launch_bounds__(kBlock) void k_ekf9t(KfArgs<MdEKF9, Ekf9Params> a) 
   float lo = ld_chunk<float, CP>(a.prm.thlo, hb0, n, sl);
   Ekf9Lo<COMP, CP> cl;
   cl.load(a.prm.clo, bid, sl);
+  Ekf9GateOf<A, CP> gt;
+  gt.load(gate_dev(aa), hb0, n, sl);
   tv.store(stab);
-  ekf9_tick1<LIBM, UPD, PRED, SEQ, COMP>(a, raw, have, stab, x, P, lo, cl.v);
+  ekf9_tick1<LIBM, UPD, PRED, SEQ, COMP>(aa, raw, have, stab, x, P, lo, cl.v, gt);
   if (live) {
     st_chunk<float, st_pol(CP)>(a.prm.thlo, hb0, n, sl, lo);
     cl.store(a.prm.clo, bid, sl);
+    gt.store(gate_dev(aa), hb0, n, sl);
     if constexpr (FMSKF_TILED) {
 #pragma unroll
       for (int k = 0; k < N; k++) tx.st(k, x[k]);
@@ -218,7 +234,8 @@ __global__ __launch_bounds__(kBlock) void k_isr_ekf9(KfArgs<MdEKF9, Ekf9Params> 
   L.load(c, (uint32_t)ic);
   tv.store(stab);
   if constexpr (CAN) rw = cl4.step(can, live);
-  ekf9_tick1<LIBM, true, true, SEQ, COMP>(a, raw, have, stab, x, P, lo, cl.v);
+  Ekf9Gate<false, 0> gt;  // no gated form: the row-gated handle takes the three-kernel ISR
+  ekf9_tick1<LIBM, true, true, SEQ, COMP>(a, raw, have, stab, x, P, lo, cl.v, gt);
   if (live) {
     st_chunk<float, st_pol(0)>(a.prm.thlo, hb0, n, sl, lo);
     cl.store(a.prm.clo, bid, sl);
@@ -238,9 +255,12 @@ __global__ __launch_bounds__(kBlock) void k_isr_ekf9(KfArgs<MdEKF9, Ekf9Params> 
 // Two robots per lane (256-robot chunks b and b + G of the tiled state, G the tick blocks):
 // robot B's 54 state loads and its raw record are issued before robot A's update, so they
 // stream in while A computes (see launch_ekf9).
-template <bool LIBM, bool SEQ, int CP, bool ENS = false, bool COMP = false>
-__global__ __launch_bounds__(kBlock) void k_ekf9p(KfArgs<MdEKF9, Ekf9Params> a) {
+// A block without a partner chunk computes on its own chunk again and stores nothing of it.
+template <bool LIBM, bool SEQ, int CP, bool ENS = false, bool COMP = false, class A = Ekf9Args>
+__global__ __launch_bounds__(kBlock) void k_ekf9p(A aa) {
   constexpr int N = 9, NP = 45;
+  static_assert(!ENS || std::is_same<A, Ekf9Args>::value, "no fused ensemble record with the row gate");
+  const Ekf9Args &a = kf_args(aa);
   uint32_t bid = blockIdx.x;  // the tick block (the carried fold blocks come first)
   if constexpr (ENS) {
     if (ens_fold_front<9>(a.in, bid)) return;
@@ -281,11 +301,15 @@ __global__ __launch_bounds__(kBlock) void k_ekf9p(KfArgs<MdEKF9, Ekf9Params> a) 
   Ekf9Lo<COMP, CP> cla, clb;
   cla.load(a.prm.clo, ta, slot(ta));
   clb.load(a.prm.clo, tb, slot(tb));
+  Ekf9GateOf<A, CP> gta, gtb;
+  gta.load(gate_dev(aa), (uint64_t)ta * kBlock, n, slot(ta));
+  gtb.load(gate_dev(aa), (uint64_t)tb * kBlock, n, slot(tb));
   tv.store(stab);
-  ekf9_tick1<LIBM, true, true, SEQ, COMP>(a, ra, ha, stab, xa, Pa, loa, cla.v);
+  ekf9_tick1<LIBM, true, true, SEQ, COMP>(aa, ra, ha, stab, xa, Pa, loa, cla.v, gta);
   if (live_a) {
     st_chunk<float, st_pol(CP)>(a.prm.thlo, (uint64_t)ta * kBlock, n, slot(ta), loa);
     cla.store(a.prm.clo, ta, slot(ta));
+    gta.store(gate_dev(aa), (uint64_t)ta * kBlock, n, slot(ta));
 #pragma unroll
     for (int k = 0; k < N; k++) txa.st(k, xa[k]);
 #pragma unroll
@@ -297,10 +321,11 @@ __global__ __launch_bounds__(kBlock) void k_ekf9p(KfArgs<MdEKF9, Ekf9Params> a) 
 #pragma unroll
     for (int k = 0; k < N; k++) xs[0][k] = xa[k];
   }
-  ekf9_tick1<LIBM, true, true, SEQ, COMP>(a, rb, hb, stab, xb, Pb, lob, clb.v);
+  ekf9_tick1<LIBM, true, true, SEQ, COMP>(aa, rb, hb, stab, xb, Pb, lob, clb.v, gtb);
   if (live_b) {
     st_chunk<float, st_pol(CP)>(a.prm.thlo, (uint64_t)tb * kBlock, n, slot(tb), lob);
     clb.store(a.prm.clo, tb, slot(tb));
+    gtb.store(gate_dev(aa), (uint64_t)tb * kBlock, n, slot(tb));
 #pragma unroll
     for (int k = 0; k < N; k++) txb.st(k, xb[k]);
 #pragma unroll
@@ -600,62 +625,75 @@ static int launch_ekf9_ens(KfArgs<MdEKF9, Ekf9Params> a, const DevState &s, bool
   return (int)g;
 }
 
-template <bool SEQ, bool COMP>
-static int launch_ekf9_s(const KfArgs<MdEKF9, Ekf9Params> &a, const DevState &s, const TickIn &in, bool libm,
-                         bool upd, bool pred, bool nt, hipStream_t st, int *ens_nb) {
-  const dim3 g = grid_for(s.n);
-  if (in.ens_blocks) {
-    *ens_nb = libm ? launch_ekf9_ens<true, SEQ, COMP>(a, s, nt, st) : launch_ekf9_ens<false, SEQ, COMP>(a, s, nt, st);
-    return (int)hipGetLastError();
-  }
-  // Single-tick kernel: two robots per lane (k_ekf9p) while the 216-byte state fits the 256 MiB
-  // Infinity Cache, else one per lane (k_ekf9t); FMSKF_EKF9_VARIANT (read once) forces one of
-  // them, 2 = k_ekf9p, 4 = k_ekf9t (the tests' cross-check at small N).  Measured (kbench, one
-  // box, two passes): 2^20 k_ekf9t 74.8-74.9 us, k_ekf9p 71.2-71.9; 2^22 (HBM) k_ekf9t 336-338,
-  // k_ekf9p 339.  A raised-priority load phase (s_setprio 3 while issuing the loads) measured
-  // 71.2-73.9 at 2^20 and 342-343 at 2^22 and was removed.
+// The launch regime of a single full tick, shared by the plain and the row-gated handles: two
+// robots per lane (k_ekf9p) while the state -- sb bytes per robot, with the gate word where there
+// is one -- fits the 256 MiB Infinity Cache, else one per lane (k_ekf9t); FMSKF_EKF9_VARIANT
+// (read once) forces one of them, 2 = k_ekf9p, 4 = k_ekf9t (the tests' cross-check at small N).
+// Measured (kbench, one box, two passes): 2^20 k_ekf9t 74.8-74.9 us, k_ekf9p 71.2-71.9; 2^22
+// (HBM) k_ekf9t 336-338, k_ekf9p 339.  A raised-priority load phase (s_setprio 3 while issuing
+// the loads) measured 71.2-73.9 at 2^20 and 342-343 at 2^22 and was removed.
+struct Ekf9Regime {
+  bool two;
+  unsigned lds;
+};
+static Ekf9Regime ekf9_regime(uint64_t n, uint64_t sb, bool libm, bool nt) {
   static const int var = [] {
     const char *e = getenv("FMSKF_EKF9_VARIANT");
     return e ? atoi(e) : 0;
   }();
-  const int v = var == 2 || var == 4 ? var : (s.n * (COMP ? 240 : 220) <= (256ull << 20) ? 2 : 4);
-  if (FMSKF_TILED && in.n_ticks == 1 && upd && pred && !libm && v == 2) {
-    const uint32_t ntiles = (uint32_t)((s.n + kBlock - 1) / kBlock);
-    const dim3 g2((ntiles + 1) / 2);
-    // 64 KiB of dynamic LDS (2 blocks per CU): 2^20 71.2 -> 70.5-70.7 us (two passes)
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_EKF9P_LDS", true, 64u * 1024u);
-    if (nt) k_ekf9p<false, SEQ, kStateNT, false, COMP><<<g2, kBlock, lds, st>>>(a);
-    else k_ekf9p<false, SEQ, 0, false, COMP><<<g2, kBlock, lds, st>>>(a);
-    return (int)hipGetLastError();
-  }
-  // predict-only launches run no update: one (SEQ = false) instantiation serves both
-  if (in.n_ticks == 1) {
-    if (libm) {
-      if (upd && pred && nt) k_ekf9t<true, true, true, SEQ, kStateNT, false, COMP><<<g, kBlock, 0, st>>>(a);
-      else if (upd && pred) k_ekf9t<true, true, true, SEQ, 0, false, COMP><<<g, kBlock, 0, st>>>(a);
-      else if (upd) k_ekf9t<true, true, false, SEQ, 0, false, COMP><<<g, kBlock, 0, st>>>(a);
-      else k_ekf9t<true, false, true, false, 0, false, COMP><<<g, kBlock, 0, st>>>(a);
-    } else {
-      // Past the Infinity Cache (non-temporal state) the occupancy is capped at 2 blocks per CU
-      // with 64 KiB of dynamic LDS: fewer concurrent tile streams per HBM channel.  2^22:
-      // 334.3-338.7 us uncapped, 332 at 32 KiB, 329.7-331.0 at 48 KiB, 326.8-330.9 at 64 KiB,
-      // 382-383 at 80 KiB (kbench, two boxes, two passes each); the same-bytes tiled pattern
-      // (membench) 299 us.  FMSKF_EKF9_LDS overrides the byte count.
-      const unsigned lds = FMSKF_LDS_CAP("FMSKF_EKF9_LDS", nt, 64u * 1024u);
-      if (upd && pred && nt) k_ekf9t<false, true, true, SEQ, kStateNT, false, COMP><<<g, kBlock, lds, st>>>(a);
-      else if (upd && pred) k_ekf9t<false, true, true, SEQ, 0, false, COMP><<<g, kBlock, lds, st>>>(a);
-      else if (upd) k_ekf9t<false, true, false, SEQ, 0, false, COMP><<<g, kBlock, 0, st>>>(a);
-      else k_ekf9t<false, false, true, false, 0, false, COMP><<<g, kBlock, 0, st>>>(a);
+  const int v = var == 2 || var == 4 ? var : (n * sb <= (256ull << 20) ? 2 : 4);
+  // 64 KiB of dynamic LDS (2 blocks per CU): 2^20 71.2 -> 70.5-70.7 us (two passes)
+  if (FMSKF_TILED && !libm && v == 2) return {true, FMSKF_LDS_CAP("FMSKF_EKF9P_LDS", true, 64u * 1024u)};
+  if (libm) return {false, 0u};
+  // Past the Infinity Cache (non-temporal state) the occupancy is capped at 2 blocks per CU
+  // with 64 KiB of dynamic LDS: fewer concurrent tile streams per HBM channel.  2^22:
+  // 334.3-338.7 us uncapped, 332 at 32 KiB, 329.7-331.0 at 48 KiB, 326.8-330.9 at 64 KiB,
+  // 382-383 at 80 KiB (kbench, two boxes, two passes each); the same-bytes tiled pattern
+  // (membench) 299 us.  FMSKF_EKF9_LDS overrides the byte count.
+  return {false, FMSKF_LDS_CAP("FMSKF_EKF9_LDS", nt, 64u * 1024u)};
+}
+
+// A: Ekf9Args, or RowGateArgs for a row-gated handle (update launches with a diagonal R only:
+// launch_ekf9_rowgate); sb: state (+ gate word) bytes per robot, nt: whether they stream
+template <bool LIBM, bool SEQ, bool COMP, class A>
+static void launch_ekf9_l(const A &aa, uint64_t sb, bool upd, bool pred, bool nt, hipStream_t st) {
+  constexpr bool GATED = std::is_same<A, RowGateArgs>::value;
+  const Ekf9Args &a = kf_args(aa);
+  const dim3 g = grid_for(a.n);
+  if (a.in.n_ticks != 1) {
+    if (upd && pred) k_ekf9<LIBM, true, true, SEQ, COMP, A><<<g, kBlock, 0, st>>>(aa);
+    else if constexpr (!GATED) {
+      if (upd) k_ekf9<LIBM, true, false, SEQ, COMP><<<g, kBlock, 0, st>>>(aa);
+      else k_ekf9<LIBM, false, true, false, COMP><<<g, kBlock, 0, st>>>(aa);
     }
-  } else if (libm) {
-    if (upd && pred) k_ekf9<true, true, true, SEQ, COMP><<<g, kBlock, 0, st>>>(a);
-    else if (upd) k_ekf9<true, true, false, SEQ, COMP><<<g, kBlock, 0, st>>>(a);
-    else k_ekf9<true, false, true, false, COMP><<<g, kBlock, 0, st>>>(a);
-  } else {
-    if (upd && pred) k_ekf9<false, true, true, SEQ, COMP><<<g, kBlock, 0, st>>>(a);
-    else if (upd) k_ekf9<false, true, false, SEQ, COMP><<<g, kBlock, 0, st>>>(a);
-    else k_ekf9<false, false, true, false, COMP><<<g, kBlock, 0, st>>>(a);
+  } else if (upd && pred) {
+    const Ekf9Regime r = ekf9_regime(a.n, sb, LIBM, nt);
+    if constexpr (!LIBM) {
+      if (r.two) {
+        const uint32_t ntiles = (uint32_t)((a.n + kBlock - 1) / kBlock);
+        const dim3 g2((ntiles + 1) / 2);
+        if (nt) k_ekf9p<false, SEQ, kStateNT, false, COMP, A><<<g2, kBlock, r.lds, st>>>(aa);
+        else k_ekf9p<false, SEQ, 0, false, COMP, A><<<g2, kBlock, r.lds, st>>>(aa);
+        return;
+      }
+    }
+    if (nt) k_ekf9t<LIBM, true, true, SEQ, kStateNT, false, COMP, A><<<g, kBlock, r.lds, st>>>(aa);
+    else k_ekf9t<LIBM, true, true, SEQ, 0, false, COMP, A><<<g, kBlock, r.lds, st>>>(aa);
+  } else if (upd) {
+    k_ekf9t<LIBM, true, false, SEQ, 0, false, COMP, A><<<g, kBlock, 0, st>>>(aa);
+  } else if constexpr (!GATED) {
+    // predict-only launches run no update: one (SEQ = false) instantiation serves both
+    k_ekf9t<LIBM, false, true, false, 0, false, COMP><<<g, kBlock, 0, st>>>(aa);
   }
+}
+
+template <bool SEQ, bool COMP>
+static int launch_ekf9_s(const Ekf9Args &a, const DevState &s, const TickIn &in, bool libm, bool upd, bool pred,
+                         bool nt, hipStream_t st, int *ens_nb) {
+  if (in.ens_blocks)
+    *ens_nb = libm ? launch_ekf9_ens<true, SEQ, COMP>(a, s, nt, st) : launch_ekf9_ens<false, SEQ, COMP>(a, s, nt, st);
+  else if (libm) launch_ekf9_l<true, SEQ, COMP>(a, COMP ? 240 : 220, upd, pred, nt, st);
+  else launch_ekf9_l<false, SEQ, COMP>(a, COMP ? 240 : 220, upd, pred, nt, st);
   return (int)hipGetLastError();
 }
 
@@ -676,6 +714,25 @@ int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool l
                          : launch_ekf9_s<false, true>(a, s, in, libm, upd, pred, nt, st, ens_nb);
   return diag ? launch_ekf9_s<true, false>(a, s, in, libm, upd, pred, nt, st, ens_nb)
               : launch_ekf9_s<false, false>(a, s, in, libm, upd, pred, nt, st, ens_nb);
+}
+
+// The row-gated handle (fmskf_set_row_gate): the same kernels on RowGateArgs through the same
+// regimes, 228 B of state + gate word per robot.  No fused ensemble record, no ISR form, no
+// compensated positions: the callers take the stand-alone record / the three-kernel ISR / refuse
+// the gate.
+int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p, const RowGateDev &g,
+                        bool libm, bool pred, hipStream_t st) {
+  if (!FMSKF_TILED || !s.tile || !s.thlo || s.xlo || in.ens_blocks || in.fold_blocks || !in.raw || !g.word ||
+      !g.d2 || g.d2_pitch < s.n || !ekf9_r_diagonal(p.r))
+    return (int)hipErrorInvalidValue;
+  if (!pred && in.n_ticks != 1) return (int)hipErrorInvalidValue;
+  RowGateArgs ga{{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p}, g};
+  ga.k.prm.thlo = s.thlo;
+  ga.k.prm.clo = nullptr;
+  const bool nt = state_nt(s.n * 228);
+  if (libm) launch_ekf9_l<true, true, false>(ga, 228, true, pred, nt, st);
+  else launch_ekf9_l<false, true, false>(ga, 228, true, pred, nt, st);
+  return (int)hipGetLastError();
 }
 
 template <bool LIBM, bool SEQ, bool COMP, bool CAN, bool CNT>

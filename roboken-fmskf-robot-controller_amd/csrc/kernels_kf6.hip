@@ -18,6 +18,10 @@
 //  * whether a validity mask exists is a compile-time choice (no conditional load whose
 //    merge would force a full vmcnt(0) drain);
 //  * tick_many loads the inputs of tick t+1 before computing tick t.
+//
+// The chi-square innovation gate (fmskf_set_gate) is an instantiation of the same kernels on
+// GateArgs (kf6_lane.hpp): one more lane struct loaded with the state and stored with it, the
+// gated update inside kf6_tick1, the launch regimes of the plain handle (kf6_regime).
 #include "ens_device.hpp"
 #include "kf6_lane.hpp"
 
@@ -44,9 +48,11 @@ static_assert(2 * kBlock + 1 == 513, "table staging assumes 256-thread blocks");
 // tick_many: T ticks per launch, state in VGPRs throughout; the inputs of the next tick are
 // loaded while the current one computes.  Unrolled by two with ping-pong input registers
 // (ma / mb) so no input record is copied around the loop; clamped index, no live branch.
-template <int WPE, class O>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6(
-    KfArgs<MdKF6, Kf6Params> a) {
+// A: Kf6Args, or GateArgs for a gated handle (every tick kernel here): the lane's gate state is
+// loaded with the other loads and stored with the state, the gate word held across the ticks.
+template <int WPE, class O, class A = Kf6Args>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6(A aa) {
+  const Kf6Args &a = kf_args(aa);
   __shared__ float stab[O::LIBM ? 1 : 513];
   const uint64_t n = a.n;
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -55,21 +61,24 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   const uint32_t T = a.in.n_ticks;
   float x[6], P[21];
   Kf6Lo<O> lo;
+  Kf6GateOf<O, A> gt;
   Kf6In ma, mb;
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
   kf6_load_lo<O>(a.prm.lo, ic, lo);
+  gt.load(gate_dev(aa), ic, n);
   if (O::UPD) ma = kf6_load_in<O>(a.in, n, 0, ic);
   stage_table<O::LIBM>(stab, a.in.sintab);
   for (uint32_t t = 0; t < T; t += 2) {
     if (O::UPD && t + 1 < T) mb = kf6_load_in<O>(a.in, n, t + 1, ic);
-    kf6_tick1<O>(ma, stab, a.prm, x, P, lo);
+    kf6_tick1<O>(ma, stab, a.prm, x, P, lo, gt);
     if (t + 1 >= T) break;
     if (O::UPD && t + 2 < T) ma = kf6_load_in<O>(a.in, n, t + 2, ic);
-    kf6_tick1<O>(mb, stab, a.prm, x, P, lo);
+    kf6_tick1<O>(mb, stab, a.prm, x, P, lo, gt);
   }
   if (live) {
     kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
     kf6_store_lo<O>(a.prm.lo, i, lo);
+    gt.store(gate_dev(aa), i, n);
   }
   nan_guard(x, P, a.counters, live);
 }
@@ -77,9 +86,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
 // Single tick, straight line: no tick loop (so no loop-carried register copies) and no
 // live/dead branch around the loads: lanes past N load instance N-1 (a clamped index, always
 // in bounds), compute on it, and only their stores and NaN count are masked off.
+// No gated instantiation: a gated handle's one-per-lane launches take k_kf6p with R = 1 (launch_one).
 template <int WPE, class O>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6t(
-    KfArgs<MdKF6, Kf6Params> a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6t(Kf6Args a) {
   uint32_t bid = blockIdx.x;
   if constexpr (O::ENS) {
     if (ens_fold_front<6>(a.in, bid)) return;
@@ -96,11 +105,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   float *stab = wtab[O::LIBM ? 0 : threadIdx.x >> 6];
   WaveTable<O::LIBM> tv(a.in.sintab);
   Kf6Lo<O> lo;
+  Kf6Gate<O, false> gt;
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
   kf6_load_lo<O>(a.prm.lo, ic, lo);
   if (O::UPD) m = kf6_load_in<O>(a.in, n, 0, ic);
   tv.store(stab);
-  kf6_tick1<O>(m, stab, a.prm, x, P, lo);
+  kf6_tick1<O>(m, stab, a.prm, x, P, lo, gt);
   if (live) {
     kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
     kf6_store_lo<O>(a.prm.lo, i, lo);
@@ -118,9 +128,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
 // R robots per lane (i, i + G, ..., G = the tick blocks' lane count), the tick inputs of all R
 // loaded up front: robot r's inputs (fresh from HBM) arrive while robots 0..r-1 are loaded,
 // computed and stored; one register set for the state, 1/R of the grid.
-template <int WPE, int R, class O>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6p(
-    KfArgs<MdKF6, Kf6Params> a) {
+template <int WPE, int R, class O, class A = Kf6Args>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6p(A aa) {
+  const Kf6Args &a = kf_args(aa);
   uint32_t bid = blockIdx.x;
   if constexpr (O::ENS) {
     if (ens_fold_front<6>(a.in, bid)) return;
@@ -145,13 +155,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
     const uint32_t i = i0 + r * G;
     const bool live = i < nn;
     Kf6Lo<O> lo;
+    Kf6GateOf<O, A> gt;
     kf6_load_state<O>(a.x, a.P, a.pitch, live ? i : last, x, P);
     kf6_load_lo<O>(a.prm.lo, live ? i : last, lo);
+    gt.load(gate_dev(aa), live ? i : last, n);
     if (r == 0) tv.store(stab);
-    kf6_tick1<O>(m[r], stab, a.prm, x, P, lo);
+    kf6_tick1<O>(m[r], stab, a.prm, x, P, lo, gt);
     if (live) {
       kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
       kf6_store_lo<O>(a.prm.lo, i, lo);
+      gt.store(gate_dev(aa), i, n);
     }
     nan_guard(x, P, a.counters, live);
     if constexpr (O::ENS) {
@@ -179,25 +192,24 @@ static int kf6_variant() {
   return v;
 }
 
-template <class O>
-static void launch_o(const KfArgs<MdKF6, Kf6Params> &a, hipStream_t st) {
-  const int v = a.in.n_ticks == 1 ? kf6_variant() : 0;
-  // state bytes per robot (COMP: + the five low-part rows) and with one tick's 16-byte inputs
-  constexpr uint64_t SB = O::COMP ? 128 : 108, RB = SB + 16;
-  if (a.in.n_ticks == 1 && v == 12) {
-    const unsigned g = (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock));
-    if constexpr (O::UPD && O::PRED) {
-      if (state_nt(a.n * SB)) {
-        k_kf6p<4, 2, WithNT<O>><<<g, kBlock, 0, st>>>(a);
-        return;
-      }
-    }
-    k_kf6p<4, 2, O><<<g, kBlock, 0, st>>>(a);
-  } else if (a.in.n_ticks == 1 && v == 0 && a.n * RB <= (256ull << 20)) {
+// The launch regime of a single tick / predict / correct, shared by the plain and the gated
+// handles: two robots per lane or one, whether the state streams past the caches (nt), the
+// dynamic-LDS occupancy cap.  sb: state bytes per robot, with the gate word and NIS where there
+// are any.  two_nt: the caller has a streamed two-per-lane kernel (the gated family has none:
+// its streamed state always goes one robot per lane)
+struct Kf6Regime {
+  bool two, nt;
+  unsigned lds;
+};
+static Kf6Regime kf6_regime(uint64_t n, uint64_t sb, bool rec, bool two_nt) {
+  const int v = kf6_variant();
+  const uint64_t rb = sb + 16;  // with one tick's 16-byte inputs
+  const bool nt = state_nt(n * sb);
+  if ((two_nt || !nt) && (v == 12 || (v == 0 && n * rb <= (256ull << 20)))) {
     // state + one tick's inputs resident in the 256 MiB Infinity Cache: two robots per lane,
     // both robots' inputs loaded up front, one wave round (2^20: 39.7 -> 37.4-38.1 us,
     // 2^21: 75.9 -> 71.5; at 2^24, HBM-bound, it is 3% slower than one robot per lane)
-    const unsigned g = (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock));
+    if (v == 12) return {true, nt, 0u};
     // 32 KiB of dynamic LDS: at most 5 blocks per CU.  kbench, records, two passes: 2^20
     // 38.2-38.5 -> 37.2-37.3 us (24 KiB 37.6-37.7, 40 KiB 37.4-37.5); 2^21 71.6-71.8 -> 70.5-70.9.
     // Records fed while state + inputs fill at most half the cache (2^20 robots): 48 KiB, 3
@@ -205,29 +217,59 @@ static void launch_o(const KfArgs<MdKF6, Kf6Params> &a, hipStream_t st) {
     // 48 KiB 36.67-36.93, 64 KiB 36.61-36.97, 80 KiB 44.0, uncapped 38.0).  Plane inputs and
     // 2^21 records stay at 32 KiB (48 KiB: 2^20 planes 37.49 -> 37.72-38.07, 2^21 records
     // 68.3-68.4 -> 69.0, 2^21 planes 69.5-69.7 -> 71.2-71.4)
-    const bool rec_half = a.in.rec != nullptr && a.n * RB <= (128ull << 20);
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF6P_LDS", true, rec_half ? 48u * 1024u : 32u * 1024u);
-    if constexpr (O::UPD && O::PRED) {
-      if (state_nt(a.n * SB)) {  // only when forced: this branch's state fits the cache
-        k_kf6p<4, 2, WithNT<O>><<<g, kBlock, lds, st>>>(a);
-        return;
-      }
-    }
-    k_kf6p<4, 2, O><<<g, kBlock, lds, st>>>(a);
-  } else if (a.in.n_ticks == 1 && (v == 0 || v == 15)) {
-    // past the Infinity Cache: at most 3 blocks per CU (48 KiB of dynamic LDS).  2^24, records,
-    // kbench, one box, two passes: 691-704 us uncapped, 671-684 at 32 KiB, 627-641 at 48 KiB,
-    // 626-639 at 64 KiB, 809-826 at 80 KiB (two blocks of 4 waves per CU are too few)
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF6_LDS", state_nt(a.n * SB), 48u * 1024u);
-    if constexpr (O::UPD && O::PRED) {
-      if (state_nt(a.n * SB)) {
-        k_kf6t<4, WithNT<O>><<<grid_for(a.n), kBlock, lds, st>>>(a);
-        return;
-      }
-    }
-    k_kf6t<4, O><<<grid_for(a.n), kBlock, lds, st>>>(a);
+    const bool rec_half = rec && n * rb <= (128ull << 20);
+    return {true, nt, FMSKF_LDS_CAP("FMSKF_KF6P_LDS", true, rec_half ? 48u * 1024u : 32u * 1024u)};
+  }
+  // past the Infinity Cache: at most 3 blocks per CU (48 KiB of dynamic LDS).  2^24, records,
+  // kbench, one box, two passes: 691-704 us uncapped, 671-684 at 32 KiB, 627-641 at 48 KiB,
+  // 626-639 at 64 KiB, 809-826 at 80 KiB (two blocks of 4 waves per CU are too few)
+  return {false, nt, FMSKF_LDS_CAP("FMSKF_KF6_LDS", nt, 48u * 1024u)};
+}
+
+// One robot per lane: k_kf6t, or for a gated handle k_kf6p's single-robot form, the shape its
+// one-per-lane launches always had (the inputs are loaded ahead of the state; through k_kf6t the
+// gated tick at 2^24 measured 642-643 us against 633, profiles/gate_fold_ab.json)
+template <class O, class A>
+static void launch_one(const A &aa, unsigned lds, hipStream_t st) {
+  const dim3 g = grid_for(kf_args(aa).n);
+  if constexpr (std::is_same<A, GateArgs>::value) k_kf6p<4, 1, O, A><<<g, kBlock, lds, st>>>(aa);
+  else k_kf6t<4, O><<<g, kBlock, lds, st>>>(aa);
+}
+
+// A: Kf6Args, or GateArgs for a gated handle (bytes per robot: + the gate word and the NIS)
+template <class O, class A>
+static void launch_o(const A &aa, hipStream_t st) {
+  constexpr bool GATED = std::is_same<A, GateArgs>::value;
+  const Kf6Args &a = kf_args(aa);
+  if constexpr (GATED && !O::PRED) {  // the gated fmskf_correct: one robot per lane, uncapped
+    launch_one<O>(aa, 0u, st);
   } else {
-    k_kf6<4, O><<<grid_for(a.n), kBlock, 0, st>>>(a);
+    if (a.in.n_ticks != 1) {
+      k_kf6<4, O, A><<<grid_for(a.n), kBlock, 0, st>>>(aa);
+      return;
+    }
+    const Kf6Regime r = kf6_regime(a.n, O::COMP ? 128 : GATED ? 116 : 108, a.in.rec != nullptr, !GATED);
+    // the streamed (non-temporal) kernels exist for the full tick only; in a two-per-lane launch
+    // only when forced, since that regime's state fits the cache
+    constexpr bool NT = O::UPD && O::PRED;
+    if (r.two) {
+      const unsigned g = (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock));
+      if constexpr (NT && !GATED) {
+        if (r.nt) {
+          k_kf6p<4, 2, WithNT<O>, A><<<g, kBlock, r.lds, st>>>(aa);
+          return;
+        }
+      }
+      k_kf6p<4, 2, O, A><<<g, kBlock, r.lds, st>>>(aa);
+      return;
+    }
+    if constexpr (NT) {
+      if (r.nt) {
+        launch_one<WithNT<O>>(aa, r.lds, st);
+        return;
+      }
+    }
+    launch_one<O>(aa, r.lds, st);
   }
 }
 
@@ -320,6 +362,32 @@ int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool lib
     else if (upd) launch_lup<false, true, false>(a, small, valid, st, nullptr);
     else launch_lup<false, false, true>(a, small, false, st, nullptr);
   }
+  return (int)hipGetLastError();
+}
+
+// The gated handle (fmskf_set_gate): the same kernels on GateArgs through the same regimes.
+// Input descriptors are always the chunk-based form that is valid for any N (kf6_load_in without
+// SMALL).  No fused ensemble record and no compensated positions: the callers take the
+// stand-alone record / refuse the gate.
+template <bool LIBM, bool PRED>
+static void launch_gate_lp(const GateArgs &ga, hipStream_t st) {
+  const bool valid = ga.k.in.valid != nullptr;
+  if (ga.k.in.rec) {
+    if (valid) launch_o<Opt<LIBM, true, PRED, false, true, true>>(ga, st);
+    else launch_o<Opt<LIBM, true, PRED, false, false, true>>(ga, st);
+  } else {
+    if (valid) launch_o<Opt<LIBM, true, PRED, false, true, false>>(ga, st);
+    else launch_o<Opt<LIBM, true, PRED, false, false, false>>(ga, st);
+  }
+}
+
+int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,
+                    bool pred, hipStream_t st) {
+  if (p.lo || in.ens_blocks || in.fold_blocks || !g.word || !g.nis) return (int)hipErrorInvalidValue;
+  if (!pred && in.n_ticks != 1) return (int)hipErrorInvalidValue;
+  const GateArgs ga{{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p}, g};
+  if (libm) pred ? launch_gate_lp<true, true>(ga, st) : launch_gate_lp<true, false>(ga, st);
+  else pred ? launch_gate_lp<false, true>(ga, st) : launch_gate_lp<false, false>(ga, st);
   return (int)hipGetLastError();
 }
 

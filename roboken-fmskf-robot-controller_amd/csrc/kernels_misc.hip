@@ -13,6 +13,7 @@
 
 #include "fmskf_device.hpp"
 #include "fmskf_internal.hpp"
+#include "kf_generic.hpp"
 #include "lane_rs.hpp"
 #include "ens_device.hpp"
 
@@ -383,6 +384,41 @@ int launch_readout(const DevState &s, float *out, hipStream_t st) {
     case 3: k_readout<3><<<g, kBlock, 0, st>>>(s.x, s.n, s.pitch, s.tile, out); break;
     default: return (int)hipErrorInvalidValue;
   }
+  return (int)hipGetLastError();
+}
+
+// fmskf_get_gate: the KF6 gate words (fmskf_internal.hpp GateDev) into status, run, rejects
+__global__ __launch_bounds__(kBlock) void k_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status,
+                                                        uint8_t *run, uint32_t *rejects) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t w = word[i];
+  if (status) status[i] = (uint8_t)(w & 3u);
+  if (run) run[i] = (uint8_t)((w >> kGateRunShift) & kGateRunMax);
+  if (rejects) rejects[i] = w >> kGateRejShift;
+}
+
+int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
+                       hipStream_t st) {
+  k_gate_unpack<<<grid_for(n), kBlock, 0, st>>>(word, n, status, run, rejects);
+  return (int)hipGetLastError();
+}
+
+// fmskf_get_row_gate: the EKF9 row-gate words into status [6][N] and run [6][N] planes
+__global__ __launch_bounds__(kBlock) void k_rowgate_unpack(const uint64_t *word, uint64_t n, uint8_t *status,
+                                                           uint8_t *run) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t w = word[i];
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+    if (status) status[a * n + i] = (uint8_t)((w >> (2 * a)) & 3u);
+    if (run) run[a * n + i] = (uint8_t)((w >> (kRowGateRunShift + 8 * a)) & kRowGateRunMax);
+  }
+}
+
+int launch_rowgate_unpack(const uint64_t *word, uint64_t n, uint8_t *status, uint8_t *run, hipStream_t st) {
+  k_rowgate_unpack<<<grid_for(n), kBlock, 0, st>>>(word, n, status, run);
   return (int)hipGetLastError();
 }
 

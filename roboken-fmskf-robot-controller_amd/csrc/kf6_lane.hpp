@@ -1,8 +1,10 @@
 // kf6_lane.hpp -- one robot's 6-state KF tick as lane functions (inputs, state load / store,
-// measurement frontend, update + predict), shared by the KF6 tick kernels (kernels_kf6.hip)
-// and the fused firmware ISR (kernels_ctrl.hip k_isr_kf6).  Canonical operation order of the
-// oracle (orc_kf6_tick), so every kernel built from these is bit-exact to it.
+// measurement frontend, update + predict, the optional gate state), shared by the KF6 tick
+// kernels (kernels_kf6.hip, plain and gated instantiations) and the fused firmware ISR
+// (kernels_ctrl.hip k_isr_kf6).  Canonical operation order of the oracle (orc_kf6_tick), so
+// every kernel built from these is bit-exact to it.
 #pragma once
+#include <type_traits>
 #include "kf_generic.hpp"
 
 #pragma clang fp contract(off)
@@ -44,6 +46,21 @@ struct Kf6In {
   uint2 rpm;
   uint32_t valid;
 };
+
+// Kernel arguments.  A handle with the chi-square innovation gate (fmskf_set_gate) launches the
+// same tick kernels instantiated on GateArgs: the plain arguments embedded as they are (nothing
+// is added to KfArgs / TickIn / Kf6Params, so the plain kernels' argument offsets do not move),
+// then the gate.
+using Kf6Args = KfArgs<MdKF6, Kf6Params>;
+struct GateArgs {
+  Kf6Args k;
+  GateDev g;
+};
+struct NoGate {};
+__host__ __device__ __forceinline__ const Kf6Args &kf_args(const Kf6Args &a) { return a; }
+__host__ __device__ __forceinline__ const Kf6Args &kf_args(const GateArgs &a) { return a.k; }
+__device__ __forceinline__ NoGate gate_dev(const Kf6Args &) { return {}; }
+__device__ __forceinline__ const GateDev &gate_dev(const GateArgs &a) { return a.g; }
 
 template <int CP = 0>
 __device__ __forceinline__ float ld_f32(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff) {
@@ -180,6 +197,48 @@ __device__ __forceinline__ void kf6_store_lo(float *lg, uint32_t i, const Kf6Lo<
   }
 }
 
+// The lane's gate state (fmskf_internal.hpp GateDev): the robot's gate word read and written (the
+// tick loop holds it across its ticks), the NIS of the launch's last measurement written when
+// there was one -- two plain [N] planes addressed per 256-robot chunk through scalar descriptors
+// like the inputs, with the state's cache policy: 12 B per robot-tick on top of the plain tick's
+// 232.  The chunk of instance ic (clamped, so in bounds) is wave-uniform, since a wave's lanes --
+// the clamped ones included -- lie in one chunk.  Without a gate (ON false) the struct is empty
+// and its members compile to nothing.
+__device__ __forceinline__ uint32_t gate_chunk(uint32_t ic) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane(ic) & ~(uint32_t)(kBlock - 1);
+}
+template <class O, bool ON_>
+struct Kf6Gate {
+  static constexpr bool ON = false;
+  __device__ __forceinline__ void load(NoGate, uint32_t, uint64_t) {}
+  __device__ __forceinline__ void store(NoGate, uint32_t, uint64_t) const {}
+};
+template <class O>
+struct Kf6Gate<O, true> {
+  static constexpr bool ON = true;
+  static_assert(O::UPD && !O::COMP && !O::ENS, "the gate: plain state, no fused ensemble record");
+  uint32_t hb, li, word, max_run;
+  float nis_max, nis;
+  bool seen;
+  __device__ __forceinline__ void load(const GateDev &g, uint32_t ic, uint64_t n) {
+    hb = gate_chunk(ic);
+    li = ic - hb;
+    word = ld_chunk<uint32_t, O::CP>(g.word, hb, n, li);
+    max_run = g.max_run;
+    nis_max = g.nis_max;
+    nis = 0.f;
+    seen = false;
+  }
+  // a live lane's clamped index is its own, so the slot of the load is the slot of the store
+  __device__ __forceinline__ void store(const GateDev &g, uint32_t, uint64_t n) const {
+    st_chunk<uint32_t, st_pol(O::CP)>(g.word, hb, n, li, word);
+    if (seen) st_chunk<float, st_pol(O::CP)>(g.nis, hb, n, li, nis);
+  }
+};
+// the gate struct that goes with a kernel's argument type
+template <class O, class A>
+using Kf6GateOf = Kf6Gate<O, std::is_same<A, GateArgs>::value>;
+
 // z = (deg2rad(yaw), -deg2rad(gz), wheel velocity rotated by the measured heading)
 // (imu_task_main.cpp:102-104, util_mymath.hpp:16, imu_if_wt901c.cpp:113,
 //  VD_vehicle_controller.cpp:21-33,47-51); y = z - H x with the heading innovation wrapped
@@ -203,10 +262,35 @@ __device__ __forceinline__ void kf6_innov(const Kf6In &m, const float *tab, cons
   y[3] = z3 - x[4];
 }
 
-template <class O>
+// g: the lane's gate state.  With the gate the update is split where the innovation is known:
+// S = L D L^T, U = L^-1 H P and w = L^-1 y are formed first (kf_update_factor), the NIS costs
+// four more operations on values in registers (kf_nis), and only the apply phase sits behind the
+// per-lane decision.  Rejecting lanes skip it, applying lanes run exactly the ungated operations:
+// nothing of the applied path depends on the decision, so an applied update is kf_update bit for
+// bit and a rejected one is the valid == 0 skip.  g.word is updated; g.nis / g.seen: the NIS of
+// this tick's measurement and that there was one (left alone otherwise)
+template <class O, class G>
 __device__ __forceinline__ void kf6_tick1(const Kf6In &m, const float *tab, const Kf6Params &prm,
-                                          float (&x)[6], float (&P)[21], Kf6Lo<O> &l) {
-  if (O::UPD && (!O::VALID || m.valid)) {
+                                          float (&x)[6], float (&P)[21], Kf6Lo<O> &l, G &g) {
+  if constexpr (G::ON) {
+    uint32_t status = FMSKF_GATE_NONE;
+    uint32_t run = (g.word >> kGateRunShift) & kGateRunMax, rej = g.word >> kGateRejShift;
+    if (!O::VALID || m.valid) {
+      float y[4], U[4][6], dinv[4], w[4];
+      kf6_innov<O::LIBM>(m, tab, x, y);
+      kf_update_factor<MdKF6>(P, y, prm.r, U, dinv, w);
+      const float v = kf_nis(w, dinv);
+      const bool forced = g.max_run > 0 && run >= g.max_run;
+      const bool apply = forced || v <= g.nis_max;
+      if (apply) kf_update_apply<MdKF6>(x, P, U, dinv, w);
+      status = forced ? FMSKF_GATE_FORCED : apply ? FMSKF_GATE_ACCEPTED : FMSKF_GATE_REJECTED;
+      run = apply ? 0u : min(run + 1u, kGateRunMax);
+      rej = apply ? rej : min(rej + 1u, kGateRejMax);
+      g.nis = v;
+      g.seen = true;
+    }
+    g.word = status | (run << kGateRunShift) | (rej << kGateRejShift);
+  } else if (O::UPD && (!O::VALID || m.valid)) {
     float y[4];
     kf6_innov<O::LIBM>(m, tab, x, y);
     if constexpr (O::COMP) kf_update<MdKF6, -1, float, 6, 4, 21, kKf6CXM, kKf6CPM>(x, P, y, prm.r, nullptr, l.v);

@@ -241,9 +241,10 @@ __device__ __forceinline__ void comp_norm(T (&x)[N], T (&P)[NP], T *clo) {
 }
 
 // The update in two phases, so that a caller can look at the innovation between them (the
-// chi-square gate, kernels_gate.hip): kf_update_factor forms U = L^-1 H P (in HP), D^-1 and
+// chi-square gate, kf6_lane.hpp kf6_tick1): kf_update_factor forms U = L^-1 H P (in HP), D^-1 and
 // w = L^-1 y and touches neither x nor P; kf_update_apply is x += U^T D^-1 w, P -= U^T D^-1 U.
-// kf_update is the two in sequence.
+// kf_update is the two in sequence.  kf_nis is what the caller looks at: the normalized
+// innovation squared y^T S^-1 y = sum w[a] * (w[a] / D[a]) from the factor phase's values.
 template <class Md, typename T = typename Md::T, int N = Md::N, int M = Md::M, int NP = Md::N *(Md::N + 1) / 2>
 __device__ __forceinline__ void kf_update_factor(const T (&P)[NP], const T (&y)[M], const T *R, T (&HP)[M][N],
                                                  T (&dinv)[M], T (&w)[M]) {
@@ -291,6 +292,14 @@ __device__ __forceinline__ void kf_update_factor(const T (&P)[NP], const T (&y)[
     for (int k = 0; k < a; k++) s = dfma<T>(-L[a][k], w[k], s);
     w[a] = s;
   }
+}
+
+template <typename T, int M>
+__device__ __forceinline__ T kf_nis(const T (&w)[M], const T (&dinv)[M]) {
+  T v = w[0] * (w[0] * dinv[0]);
+#pragma unroll
+  for (int a = 1; a < M; a++) v = dfma<T>(w[a], w[a] * dinv[a], v);
+  return v;
 }
 
 template <class Md, int CI = -1, typename T = typename Md::T, int N = Md::N, int M = Md::M,

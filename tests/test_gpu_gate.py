@@ -1,4 +1,4 @@
-"""The KF6 chi-square innovation gate (fmskf_set_gate / fmskf_get_gate; csrc/kernels_gate.hip) on
+"""The KF6 chi-square innovation gate (fmskf_set_gate / fmskf_get_gate; csrc/kernels_kf6.hip) on
 the GPU: the gated tick against the oracle bit for bit (the oracle skips the update of the robots
 the GPU reports as rejected), the decision and the NIS against a float64 computation on the
 pre-tick state (tests/gate_ref.py), monitor-only mode, the edges, every kernel form and fused
@@ -276,27 +276,28 @@ def test_edges(orc):
 
 # ---------------------------------------------------------------------------- 6
 def _variant_result():
-    """gated single ticks (records and planes alternating, a valid mask) and the same ticks as
-    one tick_many, at several N: the final state and gate readout of both, which must agree with
-    each other here and with every other kernel selection (FMSKF_KF6_VARIANT, FMSKF_STATE_NT)"""
+    """gated single ticks (records and planes alternating, a valid mask), the same ticks as one
+    tick_many and as correct + predict, at several N: the final state and gate readout of all,
+    which must agree with each other here and with every other kernel selection
+    (FMSKF_KF6_VARIANT, FMSKF_STATE_NT)"""
     out = {}
     Tv = 12
     for n in (1, 65, 777, 5000):
         yaw, gz, rpm, _ = gate_ref.gate_inputs(n, Tv, seed=9100 + n, start=4)
         rec = fmskf.kf6_records(yaw, gz, rpm)
         valid = (np.random.default_rng(n + 9).random((Tv, n)) > 0.2).astype(np.uint8)
-        with Engine("kf6", n) as a, Engine("kf6", n) as b, Engine("kf6", n) as c:
-            for e in (a, b, c):
+        with Engine("kf6", n) as a, Engine("kf6", n) as b, Engine("kf6", n) as c, Engine("kf6", n) as d:
+            for e in (a, b, c, d):
                 e.set_gate(NIS_MAX, MAXC)
             for t in range(Tv):
-                if t % 2:
-                    a.tick(kf6_rec=rec[t], valid=valid[t])
-                else:
-                    a.tick(yaw_deg=yaw[t], gyro_z_dps=gz[t], rpm=rpm[t], valid=valid[t])
+                kw = dict(kf6_rec=rec[t]) if t % 2 else dict(yaw_deg=yaw[t], gyro_z_dps=gz[t], rpm=rpm[t])
+                a.tick(valid=valid[t], **kw)
+                d.correct(valid=valid[t], **kw)
+                d.predict()
             b.tick_many(Tv, kf6_rec=rec, valid=valid)
             c.tick_many(Tv, yaw_deg=yaw, gyro_z_dps=gz, rpm=rpm, valid=valid)
             ga = a.get_gate()
-            for e, what in ((b, "tick_many records"), (c, "tick_many planes")):
+            for e, what in ((b, "tick_many records"), (c, "tick_many planes"), (d, "correct + predict")):
                 _same_state(a, e, f"n={n} {what}")
                 _same_gate(ga, e.get_gate(), f"n={n} {what}")
             x, P = a.get_state()

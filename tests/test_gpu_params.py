@@ -286,7 +286,7 @@ def test_comp_pos(orc, model, n):
 # ----------------------------------------------------------------------------- KF6 gate
 @pytest.mark.parametrize("case", list(pc.GATE_SEED))
 def test_gate_with_dense_r(orc, case):
-    """the KF6 innovation gate (kernels_gate.hip) with more than one R off-diagonal: after every
+    """the KF6 innovation gate (kernels_kf6.hip) with more than one R off-diagonal: after every
     tick the state is the oracle's, fed the GPU's own decisions (as test_gpu_gate._main_run); the
     status is the float64 decision outside the 1e-3 band, which holds at most 0.1 % of the
     robot-ticks (nis_max and the seeds: param_cases.GATE_*, which meet that cap on the CPU already,

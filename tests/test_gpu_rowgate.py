@@ -1,5 +1,5 @@
 """The EKF9 per-row innovation gate (fmskf_set_row_gate / fmskf_get_row_gate;
-csrc/kernels_rowgate.hip) on the GPU: the row-gated tick against the oracle run with +inf on the
+csrc/kernels_kf.hip) on the GPU: the row-gated tick against the oracle run with +inf on the
 rejected rows' R (tests/rowgate_ref.py), the decisions and the d2 planes against the float64
 sequential update on the pre-tick state, monitor-only mode, every kernel form and fused entry
 point against the single gated tick, the lifecycle (reset, checkpoint) and the argument rules.
