@@ -381,6 +381,24 @@ class Wt901Batch:
     def is_error(self):
         return _struct_view(self.s, Wt901State)["is_error"].copy()
 
+    @property
+    def regs(self):
+        """[0x90][n] register files (fmskf_get_imu_regs' layout)"""
+        return np.ascontiguousarray(_struct_view(self.s, Wt901State)["reg"].T)
+
+    @property
+    def pending(self):
+        """[n] bytes pending in the parser windows"""
+        return _struct_view(self.s, Wt901State)["cnt"].copy()
+
+    def take_cb(self):
+        """the register-update callbacks since the last call: (count [n], reg [n][64], num [n][64]);
+        the logs are emptied"""
+        v = _struct_view(self.s, Wt901State)
+        out = v["ncb"].copy(), v["cb_reg"].copy(), v["cb_num"].copy()
+        v["ncb"][:] = 0
+        return out
+
 
 class MotorBatch:
     """n robots' four MOTOR_IF_M2006 instances fed by one C call per tick (orc_can_ingest_batch)."""
@@ -667,6 +685,10 @@ class RefWt901:
         rc = RefWt901._l.ref_wt901_begin(read_reg_index)
         if rc != 0:
             raise RuntimeError(f"WitReadReg failed: {rc}")
+
+    def latch(self):
+        """what a latching poll does before its bytes (init(): WitInit, an empty parser window)"""
+        RefWt901._l.ref_wt901_latch()
 
     def feed(self, data):
         b = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8))

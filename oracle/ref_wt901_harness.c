@@ -42,6 +42,15 @@ int ref_wt901_begin(uint32_t read_reg_index) {
   return WitReadReg(read_reg_index, 1);
 }
 
+/* A latching poll is IMU_IF_WT901C::init() again (src/Imu/imu_if_wt901c.cpp:63-69): WitInit and
+ * the callback registrations, before the poll's bytes.  The register file and the index of
+ * WitReadReg stay. */
+void ref_wt901_latch(void) {
+  WitInit(WIT_PROTOCOL_NORMAL, 0x50);
+  WitSerialWriteRegister(harness_serial_write);
+  WitRegisterCallBack(harness_cb);
+}
+
 void ref_wt901_feed(const uint8_t *bytes, uint32_t len) {
   for (uint32_t i = 0; i < len; i++) WitSerialDataIn(bytes[i]);
 }
