@@ -441,17 +441,40 @@ class Engine:
         """fmskf_load_state: resume from a checkpoint of a handle of the same model and N"""
         check(load().fmskf_load_state(self.h, str(path).encode()), "load_state")
 
-    def get_pose(self):
-        out = np.empty((3, self.n), np.float32)
-        p = [out[k].ctypes.data_as(C.c_void_p) for k in range(3)]
-        check(load().fmskf_get_pose(self.h, *p, MEM_HOST), "get_pose")
+    def _planes3(self, fn, what, out, planes):
+        """a readout of three [N] float planes into `out` [3, N] float32: None (a new numpy
+        array), a C-contiguous numpy array (host) or a contiguous torch CUDA tensor (device, on
+        the handle's stream, no host wait).  planes[k] False passes NULL for plane k, whose row
+        of `out` is left as it is (zero in a new array)."""
+        planes = tuple(bool(p) for p in planes)
+        if len(planes) != 3:
+            raise ValueError(f"{what}: planes wants three flags")
+        if out is None:
+            out = np.empty((3, self.n), np.float32) if all(planes) else np.zeros((3, self.n), np.float32)
+        if tuple(out.shape) != (3, self.n):
+            raise ValueError(f"{what}: out shape {tuple(out.shape)}, want {(3, self.n)}")
+        if _is_torch(out):
+            if not out.is_cuda or not out.is_contiguous() or str(out.dtype) != "torch.float32":
+                raise TypeError(f"{what}: a torch `out` must be a contiguous float32 CUDA tensor")
+            p = [C.c_void_p(out[k].data_ptr()) if planes[k] else None for k in range(3)]
+            mem = MEM_DEVICE
+        else:
+            if not isinstance(out, np.ndarray) or out.dtype != np.float32 or not out.flags.c_contiguous \
+                    or not out.flags.writeable:
+                raise TypeError(f"{what}: a host `out` must be a writable C-contiguous float32 numpy array")
+            p = [out[k].ctypes.data_as(C.c_void_p) if planes[k] else None for k in range(3)]
+            mem = MEM_HOST
+        check(fn(self.h, *p, mem), what)
         return out
 
-    def get_vel(self):
-        out = np.empty((3, self.n), np.float32)
-        p = [out[k].ctypes.data_as(C.c_void_p) for k in range(3)]
-        check(load().fmskf_get_vel(self.h, *p, MEM_HOST), "get_vel")
-        return out
+    def get_pose(self, out=None, planes=(True, True, True)):
+        """fmskf_get_pose: [3, N] float32 (x m, y m, th rad); `out`, `planes` as _planes3"""
+        return self._planes3(load().fmskf_get_pose, "get_pose", out, planes)
+
+    def get_vel(self, out=None, planes=(True, True, True)):
+        """fmskf_get_vel: [3, N] float32 (body vx mm/s, vy mm/s, vth rad/s); `out`, `planes` as
+        _planes3"""
+        return self._planes3(load().fmskf_get_vel, "get_vel", out, planes)
 
     def get_prev_sum(self):
         out = np.empty((4, self.n), np.int64)
@@ -683,15 +706,36 @@ class Engine:
                                     MEM_HOST), "get_ctrl")
         return dict(vel_tgt=vt, curr=cur, wheel_tgt=wt, wheel_ctrl=wc)
 
-    def export_vehicle_info(self, floor=None, cam_pitch=None, fault=None):
-        """[N] VehicleInfo records (structured numpy array, VEHICLE_INFO_DTYPE)"""
+    def export_vehicle_info(self, floor=None, cam_pitch=None, fault=None, out=None):
+        """[N] VehicleInfo records: a structured numpy array (VEHICLE_INFO_DTYPE) from host
+        inputs; with `out`, an [N, 84] uint8 device tensor, the records' bytes on the device (one
+        mem flag covers the call: floor [N, 8] uint8, cam_pitch [N] float32 and fault [N] must
+        then be device tensors too, or None).  Device inputs without `out` get a new tensor."""
         a = _Args()
+        dev = None
+        # the C ABI takes bare pointers: check the device tensors' types and extents here
+        # (fault: any 32-bit integer type, torch builds differ in their uint32 support)
+        for name, v, dt, cnt in (("floor", floor, "uint8", 8 * self.n), ("cam_pitch", cam_pitch, "float32", self.n),
+                                 ("fault", fault, None, self.n)):
+            if v is not None and _is_torch(v) and v.is_cuda:
+                dev = v.device
+                ok = (v.element_size() == 4 and not v.is_floating_point()) if dt is None \
+                    else str(v.dtype) == "torch." + dt
+                if not ok or v.numel() < cnt:
+                    raise TypeError(f"{name}: dtype {v.dtype} x {v.numel()}, want {dt or 'int32'} x {cnt}")
         pf = a.ptr(floor, np.uint8)
         pc = a.ptr(cam_pitch, np.float32)
         pu = a.ptr(fault, np.uint32)
-        mem = MEM_HOST if a.mem is None else a.mem
-        if mem != MEM_HOST:
-            raise ValueError("export_vehicle_info: host inputs only from Python")
+        if out is not None or a.mem == MEM_DEVICE:
+            if out is None:
+                import torch
+                out = torch.empty((self.n, VEHICLE_INFO_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            if not (_is_torch(out) and out.is_cuda and str(out.dtype) == "torch.uint8"
+                    and out.numel() == self.n * VEHICLE_INFO_DTYPE.itemsize):
+                raise TypeError("export_vehicle_info: `out` must be an [N, 84] uint8 device tensor")
+            po = a.ptr(out)  # raises when the inputs are host arrays
+            check(load().fmskf_export_vehicle_info(self.h, po, pf, pc, pu, MEM_DEVICE), "export_vehicle_info")
+            return out
         out = np.empty(self.n, VEHICLE_INFO_DTYPE)
         check(load().fmskf_export_vehicle_info(self.h, out.ctypes.data_as(C.c_void_p), pf, pc, pu,
                                                MEM_HOST), "export_vehicle_info")
