@@ -400,6 +400,88 @@ int fmskf_correct_pose(fmskf_handle h, const fmskf_pose_fix *fixes, uint64_t cou
                        float *nis, uint8_t *status,   /* [count], either may be NULL */
                        uint32_t mem);
 
+/* ---- robots selected by their state; state of listed robots (KF6, EKF9) --------- */
+/* The per-robot signals of the entry points above -- a state gone non-finite (counter [0] says
+ * that some did, not which), a position covariance grown too large, a gate that keeps rejecting
+ * -- matter for a few robots in a million.  fmskf_select finds them on the device and writes the
+ * strictly ascending list fmskf_correct_pose and the two subset calls below take, so the caller
+ * neither copies the fleet's state to the host nor touches the rest of the fleet.
+ *
+ * A robot is selected when ANY of the requested criteria holds:
+ *   FMSKF_SEL_NONFINITE  any element of its x or packed P (the rows fmskf_get_state returns, not
+ *                        the hidden low parts) is NaN or +-Inf
+ *   FMSKF_SEL_POS_VAR    P[0][0] + P[1][1] > pos_var_min: one fp32 addition of packed rows 0 and
+ *                        2, a strict compare; a NaN sum does not select
+ *   FMSKF_SEL_GATE_RUN   consecutive rejections >= run_min: on a KF6 handle with fmskf_set_gate
+ *                        its run, on an EKF9 handle with fmskf_set_row_gate any row a with bit a
+ *                        of row_mask set and run[a] >= run_min
+ *
+ * *count receives the number of robots that match, never capped by `capacity`.
+ * robots[0 .. min(*count, capacity)) receives the matching robots in strictly ascending order --
+ * with more matches than `capacity`, the first `capacity` of them -- and reason[k], when `reason`
+ * is not NULL, the OR of the requested criteria that held for robots[k] (never 0).  Entries past
+ * that are not written.  capacity == 0 with robots == NULL is a count-only call.  Two calls on
+ * the same state write the same bytes.
+ *
+ * FMSKF_EINVAL for unknown criteria bits or none, a NaN pos_var_min (with FMSKF_SEL_POS_VAR),
+ * run_min outside 1..255 (with FMSKF_SEL_GATE_RUN), a row_mask that is not a nonzero subset of
+ * 0x3F on EKF9 with FMSKF_SEL_GATE_RUN or not 0 otherwise, FMSKF_SEL_GATE_RUN on a handle whose
+ * gate (KF6) or row gate (EKF9) is not set, a NULL count, a NULL robots with capacity > 0, and
+ * inside a graph capture.
+ *
+ * With FMSKF_MEM_HOST the call is complete on return.  With FMSKF_MEM_DEVICE robots, reason and
+ * count (8-byte aligned) are device pointers and the call is asynchronous on the handle's stream.
+ * The call reads the state and changes nothing of the handle: no persistent state, nothing in a
+ * checkpoint.  Its scratch (one flag byte per robot, one count per 256 robots) is allocated on
+ * first use and freed by fmskf_destroy.  fmskf_set_timing records the call's launches (four; the
+ * subset calls below: one) as one entry, like a tick-kernel launch.
+ *
+ * KF6 (plain and FMSKF_CFG_COMP_POS) and EKF9 (plain); FMSKF_ENOTSUP for RS, KF12D and EKF9 with
+ * FMSKF_CFG_COMP_POS -- the models of fmskf_correct_pose, for all three entry points. */
+#define FMSKF_SEL_NONFINITE 1u  /* any element of the robot's x or packed P (the hi rows) is NaN or +-Inf */
+#define FMSKF_SEL_POS_VAR   2u  /* P[0][0] + P[1][1] > pos_var_min: one fp32 addition of packed rows 0 and 2,
+                                   strict compare; a NaN sum does not select */
+#define FMSKF_SEL_GATE_RUN  4u  /* consecutive rejections >= run_min: KF6 with fmskf_set_gate its run; EKF9
+                                   with fmskf_set_row_gate any row a with bit a of row_mask set and
+                                   run[a] >= run_min */
+typedef struct fmskf_select_params {
+  uint32_t criteria;    /* FMSKF_SEL_* bits, at least one; a robot is selected when ANY of them holds */
+  float pos_var_min;    /* read only with FMSKF_SEL_POS_VAR; not NaN */
+  uint32_t run_min;     /* read only with FMSKF_SEL_GATE_RUN; 1..255 */
+  uint32_t row_mask;    /* EKF9 + FMSKF_SEL_GATE_RUN: nonzero subset of 0x3F; must be 0 otherwise */
+} fmskf_select_params;
+
+int fmskf_select(fmskf_handle h, const fmskf_select_params *prm,
+                 uint32_t *robots, uint8_t *reason,   /* [capacity]; reason may be NULL */
+                 uint64_t capacity, uint64_t *count, uint32_t mem);
+
+/* Read (get) or overwrite (set) the state of the listed robots alone.  x is [n][count], p_packed
+ * [n(n+1)/2][count] and lo [rows][count] float (rows as fmskf_get_state_lo reports it): dense
+ * planes of pitch `count`, column k is robot robots[k].  Any of the three may be NULL; a non-NULL
+ * lo on a model that keeps no low rows is FMSKF_EINVAL.
+ *
+ * get: column k equals column robots[k] of fmskf_get_state / fmskf_get_state_lo, bit for bit.
+ * set: only the listed robots' rows change, by the rules of fmskf_set_state applied per listed
+ * robot: a given x restarts the heading low part (EKF9) at 0; with FMSKF_CFG_COMP_POS a given x or
+ * p_packed restarts the position low parts at 0; a given lo replaces the restarted value.  So a
+ * get followed by a set with all three arrays restores the listed robots bit for bit.  Gate state
+ * is left alone; a set of x invalidates the ensemble shift snapshot.
+ *
+ * `robots` follows the list rules of fmskf_correct_pose: strictly ascending; a host list is
+ * validated before anything is launched (FMSKF_EINVAL for an entry that is not above its
+ * predecessor or is >= N, and nothing changes); in a device list the kernel ignores any entry that
+ * is >= N or not above the entry before it -- a get leaves that entry's output column unwritten, a
+ * set changes nothing for it -- and counts it in fmskf_get_counters slot [4].  count == 0 is
+ * FMSKF_OK with no launch; count > N is FMSKF_EINVAL.  One mem flag covers the list and the
+ * arrays.  With device pointers both calls are asynchronous on the handle's stream and can be
+ * captured by fmskf_graph_begin; a host list inside a capture is FMSKF_EINVAL.  An array past
+ * 4 GiB is reached through 64-bit lane addresses and non-temporal accesses, as in
+ * fmskf_correct_pose; FMSKF_SUBSET_BIG=1 (read once, at the first launch) forces that form. */
+int fmskf_get_state_subset(fmskf_handle h, const uint32_t *robots, uint64_t count,
+                           float *x, float *p_packed, float *lo, uint32_t mem);
+int fmskf_set_state_subset(fmskf_handle h, const uint32_t *robots, uint64_t count,
+                           const float *x, const float *p_packed, const float *lo, uint32_t mem);
+
 /* ---- readout --------------------------------------------------------------- */
 /* VEHICLE_CTRL::get_vehicle_pos_m_latest (x m, y m, th rad).  Any pointer may be NULL. */
 int fmskf_get_pose(fmskf_handle h, float *x, float *y, float *th, uint32_t mem);
@@ -459,7 +541,8 @@ int fmskf_get_motor_status(fmskf_handle h, int16_t *microsec_id, int16_t *angle,
  * [1]).  Results are identical either way; [1] and
  * [2] count since create / reset and are not checkpointed.  [3] = entries of device fix lists
  * that fmskf_correct_pose ignored as malformed (FMSKF_FIX_IGNORED); since create / reset, not
- * checkpointed either. */
+ * checkpointed either.  [4] = entries of device robot lists that fmskf_get_state_subset /
+ * fmskf_set_state_subset ignored as malformed; since create / reset, not checkpointed. */
 int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters);
 
 /* ---- ensemble statistics (mean / covariance of x across instances) --------- */

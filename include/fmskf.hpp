@@ -112,6 +112,33 @@ class Robots {
     check(fmskf_correct_pose(h_, fixes, count, &prm, nis, status, mem), "fmskf_correct_pose");
   }
 
+  // the robots for which any criterion of prm holds (fmskf_select: a state gone non-finite, a
+  // position covariance above a threshold, a gate that keeps rejecting), strictly ascending --
+  // the list correct_pose and the subset calls take.  robots / reason [capacity] (reason may be
+  // NULL; capacity 0 with robots NULL counts only); returns the number of matches, which
+  // `capacity` does not cap.  select_device takes device pointers (count too) and is asynchronous
+  // on the handle's stream.
+  uint64_t select(const fmskf_select_params &prm, uint32_t *robots, uint8_t *reason, uint64_t capacity) {
+    uint64_t total = 0;
+    check(fmskf_select(h_, &prm, robots, reason, capacity, &total, FMSKF_MEM_HOST), "fmskf_select");
+    return total;
+  }
+  void select_device(const fmskf_select_params &prm, uint32_t *robots, uint8_t *reason, uint64_t capacity,
+                     uint64_t *count) {
+    check(fmskf_select(h_, &prm, robots, reason, capacity, count, FMSKF_MEM_DEVICE), "fmskf_select");
+  }
+  // the state of the listed robots alone (strictly ascending; fmskf_get_state_subset /
+  // fmskf_set_state_subset): x [n][count], p_packed [n(n+1)/2][count], lo [rows][count], any may
+  // be NULL.  A set leaves every robot that is not listed untouched.
+  void get_state_subset(const uint32_t *robots, uint64_t count, float *x, float *p_packed, float *lo = nullptr,
+                        uint32_t mem = FMSKF_MEM_HOST) {
+    check(fmskf_get_state_subset(h_, robots, count, x, p_packed, lo, mem), "fmskf_get_state_subset");
+  }
+  void set_state_subset(const uint32_t *robots, uint64_t count, const float *x, const float *p_packed,
+                        const float *lo = nullptr, uint32_t mem = FMSKF_MEM_HOST) {
+    check(fmskf_set_state_subset(h_, robots, count, x, p_packed, lo, mem), "fmskf_set_state_subset");
+  }
+
   // VDT::can_tx_routine_intr: correct with the IMU yaw, then VEHICLE_CTRL::update (the
   // odometry / estimator time update, then the control half: interpolators, IK, FF_PI_D),
   // then M_CAN.tx_routine -- reading the device-resident IMU / motor state the ingest calls

@@ -7,6 +7,7 @@
 //   api_comm.cpp        RCCL (dlopen), the communicator, the asynchronous ensemble exchange
 //   api_ctrl.cpp        control step, CAN TX, the fused ISR, VehicleInfo, timing
 //   api_fix.cpp         fmskf_correct_pose
+//   api_select.cpp      fmskf_select, fmskf_get_state_subset / fmskf_set_state_subset
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -180,6 +181,14 @@ struct fmskf_ctx {
   // fmskf_correct_pose: malformed entries of device fix lists, counted by the kernel
   // (fmskf_get_counters [3]); a word of its own, since DevState::counters is checkpointed whole
   unsigned long long *fix_ignored = nullptr;
+  // fmskf_get_state_subset / fmskf_set_state_subset: malformed entries of device robot lists
+  // (fmskf_get_counters [4]), a word of its own for the same reason
+  unsigned long long *subset_ignored = nullptr;
+  // fmskf_select scratch, allocated on its first call (fmskf_internal.hpp SelectDev): the reason
+  // byte of every robot, the count of every 256-robot block, the scan of the chunk sums.  Not
+  // state: every call rewrites what it reads, and no checkpoint holds it.
+  uint8_t *sel_flag = nullptr;
+  uint32_t *sel_blk = nullptr, *sel_chunk = nullptr;
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
   // call) that ran as the tick, control-step and frame kernels instead of one fused kernel

@@ -165,10 +165,14 @@ int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters) 
     hip_check(hipMemcpyAsync(tmp, h->s.counters, sizeof(tmp), hipMemcpyDeviceToHost, h->stream), "D2H");
     unsigned long long ignored = 0;  // fmskf_correct_pose: malformed device-list entries
     hip_check(hipMemcpyAsync(&ignored, h->fix_ignored, sizeof(ignored), hipMemcpyDeviceToHost, h->stream), "D2H");
+    unsigned long long sub_ignored = 0;  // the subset get / set: malformed device-list entries
+    hip_check(hipMemcpyAsync(&sub_ignored, h->subset_ignored, sizeof(sub_ignored), hipMemcpyDeviceToHost, h->stream),
+              "D2H");
     hip_check(hipStreamSynchronize(h->stream), "sync");
     tmp[1] = h->isr_can_split;  // host-side counters: the launch forms the ISR calls took
     tmp[2] = h->isr_ctrl_split;
     tmp[3] = ignored;
+    tmp[4] = sub_ignored;
     for (uint32_t k = 0; k < n_counters && k < 8; k++) counters[k] = tmp[k];
   });
 }

@@ -198,6 +198,33 @@ struct PoseFixDev {
   float nis_max;
   uint32_t m;       // 2: z = (px, py); 3: z = (px, py, theta)
 };
+// One fmskf_select call as its kernels see it (kernels_select.hip; argument structs of their own,
+// nothing is added to the tick kernels').  Scratch of the handle: flag [N] the reason byte of
+// every robot (0: not selected), blk [ceil(N / 256)] the selected robots of every 256-robot block,
+// chunk [ceil(blocks / 256)] the exclusive scan of the sums of 256 block counts.
+struct SelectDev {
+  uint32_t criteria;  // FMSKF_SEL_*
+  float pos_var_min;
+  uint32_t run_min, row_mask;
+  const uint32_t *gate_word;     // KF6 gate words (GateDev::word), FMSKF_SEL_GATE_RUN
+  const uint64_t *rowgate_word;  // EKF9 row-gate words (RowGateDev::word), FMSKF_SEL_GATE_RUN
+  uint8_t *flag;
+  uint32_t *blk, *chunk;
+  uint32_t *robots;  // [capacity] or null
+  uint8_t *reason;   // [capacity] or null
+  uint64_t capacity;
+  uint64_t *count;
+};
+constexpr uint32_t kSelChunk = 256;  // block counts per scan chunk
+// One fmskf_get_state_subset / fmskf_set_state_subset call as its kernel sees it: the list and the
+// caller's dense planes of pitch `count` (device pointers; a null array is skipped)
+struct SubsetDev {
+  const uint32_t *robots;
+  uint64_t count;
+  float *x, *p, *lo;            // get: written; set: read
+  unsigned long long *ignored;  // malformed entries (fmskf_get_counters [4])
+  bool set;
+};
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -420,6 +447,11 @@ int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_
 // the absolute pose-fix update of the listed robots (kernels_fix.hip): KF6 (plain and
 // FMSKF_CFG_COMP_POS) and EKF9 (plain); hipErrorNotSupported otherwise
 int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st);
+// fmskf_select (kernels_select.hip): the flag pass over the robots, the scan of the block counts
+// (two launches), the ordered emit; the models of launch_pose_fix
+int launch_select(const DevState &s, const SelectDev &d, hipStream_t st);
+// the state of listed robots gathered into (or scattered from) the caller's planes
+int launch_state_subset(const DevState &s, const SubsetDev &d, hipStream_t st);
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
                 bool pred, hipStream_t st, int *ens_nb = nullptr);
 // the row-gated EKF9 measurement update (kernels_kf.hip), with the predict (pred) or alone;

@@ -12,21 +12,15 @@
 // FMSKF_CFG_COMP_POS, the position low parts (CXM / CPM) exactly where the models' own updates
 // have them.  A rejected or ignored lane stores nothing.
 //
-// Addressing: the state is tiled [ceil(N / 2048)][rows][2048] (fmskf_internal.hpp st_at) and a
-// wave's robots lie in arbitrary tiles, so the wave-uniform per-chunk descriptors of the tick
-// kernels do not apply.  Each array is one descriptor over the whole array (kernel arguments
-// only, so it stays in SGPRs), the lane's row-0 byte offset is its voffset and row k the scalar
-// offset k * 2048 * 4: one address register per array and the state's cache policy in the aux
-// bits.  An array past 4 GiB (KF6 beyond 51 M robots, EKF9 beyond 23 M) cannot be reached through
-// 32-bit offsets: the BIG form uses 64-bit lane addresses and non-temporal accesses (such a state
-// is always streamed).
+// Addressing: per lane through FixRows (list_rows.hpp): one whole-array descriptor, the lane's
+// row-0 byte offset as voffset, the row as a scalar offset; past 4 GiB the BIG form.
 //
 // Cost: the gathers are element-granular.  With `robot` ascending, a wave at density 1 touches
 // each row's 256 contiguous bytes; at one robot in 32 every row load of a lane touches its own
 // 128-byte line (DESIGN.md section 3 has the model and the measured numbers).
 //
 // The kernel takes its own argument struct (FixArgs): nothing is added to the tick kernels'.
-#include "kf6_lane.hpp"
+#include "list_rows.hpp"
 
 #pragma clang fp contract(off)
 
@@ -55,32 +49,6 @@ struct MdFix {
   static constexpr int N = NX, M = MM;
   __host__ __device__ static constexpr int h1(int a) { return a; }
   __host__ __device__ static constexpr int h2(int) { return -1; }
-};
-
-// ROWS tiled rows of one robot, addressed per lane
-template <int ROWS, int CP, bool BIG>
-struct FixRows {
-  static constexpr uint32_t W = tile_w<float>();
-  __amdgpu_buffer_rsrc_t r;
-  uint32_t vo;
-  float *p;
-  __device__ __forceinline__ FixRows(float *base, uint64_t pitch, uint32_t robot) {
-    const uint64_t e = (uint64_t)(robot / W) * ((uint64_t)ROWS * W) + robot % W;
-    if constexpr (BIG) {
-      p = base + e;
-    } else {
-      r = rsrc(base, (uint64_t)ROWS * pitch * sizeof(float));
-      vo = (uint32_t)e * 4u;
-    }
-  }
-  __device__ __forceinline__ float ld(int k) const {
-    if constexpr (BIG) return __builtin_nontemporal_load(p + (size_t)k * W);
-    else return ld_f32<CP>(r, vo, k * W * 4);
-  }
-  __device__ __forceinline__ void st(int k, float v) const {
-    if constexpr (BIG) __builtin_nontemporal_store(v, p + (size_t)k * W);
-    else st_f32<st_pol(CP)>(r, vo, k * W * 4, v);
-  }
 };
 
 // NX: 6 (KF6) or 9 (EKF9, with the heading low part); MM: 2 or 3; COMP: KF6's position low parts
@@ -183,7 +151,7 @@ int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st) {
   // the state's cache policy as the model's tick launcher chooses it
   const bool nt = state_nt(ekf ? s.n * 55 * 4 : s.n * (comp ? 128 : 108));
   // the largest array (P) within reach of a 32-bit byte offset?
-  const bool big = (uint64_t)(ekf ? 45 : 21) * s.pitch * sizeof(float) > 0xFFFFFFFFull;
+  const bool big = rows_big(ekf, s.pitch);
   if (ekf) {
     if (f.m == 3) launch_fix_m<9, 3, false>(a, nt, big, st);
     else launch_fix_m<9, 2, false>(a, nt, big, st);

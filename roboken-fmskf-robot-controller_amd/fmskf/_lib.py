@@ -97,6 +97,15 @@ class PoseFixParams(C.Structure):
     _fields_ = [("r", C.c_double * 6), ("nis_max", C.c_float), ("flags", C.c_uint32)]
 
 
+# fmskf_select criteria (FMSKF_SEL_*), also the bits of its reason bytes
+SEL_NONFINITE, SEL_POS_VAR, SEL_GATE_RUN = 1, 2, 4
+
+
+class SelectParams(C.Structure):
+    _fields_ = [("criteria", C.c_uint32), ("pos_var_min", C.c_float), ("run_min", C.c_uint32),
+                ("row_mask", C.c_uint32)]
+
+
 class CtrlParams(C.Structure):
     _fields_ = [(f, C.c_float) for f in ("ctrl_freq_hz", "ff_gain", "p_gain", "i_gain", "d_gain",
                                           "i_limit", "lpf_freq_hz", "ff_limit", "interp_ts")] + \
@@ -150,6 +159,9 @@ SIGNATURES = {
     "fmskf_set_row_gate": (C.c_int, [_H, C.POINTER(RowGate)]),
     "fmskf_get_row_gate": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_correct_pose": (C.c_int, [_H, _P, C.c_uint64, C.POINTER(PoseFixParams), _P, _P, C.c_uint32]),
+    "fmskf_select": (C.c_int, [_H, C.POINTER(SelectParams), _P, _P, C.c_uint64, _P, C.c_uint32]),
+    "fmskf_get_state_subset": (C.c_int, [_H, _P, C.c_uint64, _P, _P, _P, C.c_uint32]),
+    "fmskf_set_state_subset": (C.c_int, [_H, _P, C.c_uint64, _P, _P, _P, C.c_uint32]),
     "fmskf_ensemble_record_len": (C.c_int, [_H, C.POINTER(C.c_uint32)]),
     "fmskf_ensemble_partial": (C.c_int, [_H, _P, C.c_uint32]),
     "fmskf_ensemble_combine": (C.c_int, [C.c_uint32, _P, C.c_uint32, _P, _P]),

@@ -14,7 +14,8 @@ import numpy as np
 from . import _lib
 from ._lib import (MEM_DEVICE, MEM_HOST, MODEL_EKF9, MODEL_KF6, MODEL_KF12D, MODEL_NAMES,
                    MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FIX_HEADING, FmskfError,
-                   EKF9_ROWS, Gate, PoseFixParams, ROW_GATE_D2, RowGate, TickInputs, check, load)
+                   EKF9_ROWS, Gate, PoseFixParams, ROW_GATE_D2, RowGate, SEL_GATE_RUN, SEL_NONFINITE, SEL_POS_VAR,
+                   SelectParams, TickInputs, check, load)
 
 # fmskf_vehicle_info (include/fmskf.h): the VehicleInfo message layout, 84 bytes
 VEHICLE_INFO_DTYPE = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("pos_theta", "<f4"),
@@ -326,6 +327,136 @@ class Engine:
         ps = a.ptr(status) if status is not None else None
         check(load().fmskf_correct_pose(self.h, pf, count, C.byref(prm), pn, ps, mem), "correct_pose")
         return (nis, status) if nis is not None or status is not None else None
+
+    # ------------------------------------------------------------------ selection, listed robots
+    def select(self, nonfinite=False, pos_var_min=None, gate_run_min=None, row_mask=None, capacity=None,
+               out=None):
+        """fmskf_select: the robots (ascending) for which any requested criterion holds --
+        nonfinite: a NaN / Inf in x or P; pos_var_min: P[0][0] + P[1][1] > pos_var_min;
+        gate_run_min: consecutive gate rejections >= gate_run_min (KF6 with set_gate; EKF9 with
+        set_row_gate, over the rows of row_mask, default all six).  Returns (robots, reason, count):
+        count the number of matches (never capped), reason[k] the SEL_* bits that held for
+        robots[k].
+        out=None: numpy arrays trimmed to min(count, capacity) entries (capacity: default N; 0: a
+        count-only call).  out=(robots, reason): the caller's arrays of `capacity` entries (default:
+        their length), written up to min(count, capacity) and returned whole; reason may be None.
+        Host: uint32 / uint8 numpy arrays, count comes back as an int.  Device: int32 / uint8
+        torch tensors with an optional third, an int64 [1] tensor that receives the count (made
+        when absent); the call is then asynchronous on the handle's stream."""
+        prm = SelectParams()
+        prm.criteria = (SEL_NONFINITE if nonfinite else 0) | (SEL_POS_VAR if pos_var_min is not None else 0) | \
+            (SEL_GATE_RUN if gate_run_min is not None else 0)
+        prm.pos_var_min = float(pos_var_min) if pos_var_min is not None else 0.0
+        prm.run_min = int(gate_run_min) if gate_run_min is not None else 0
+        if row_mask is None:
+            row_mask = 0x3F if gate_run_min is not None and self.model == MODEL_EKF9 else 0
+        prm.row_mask = int(row_mask)
+        fn = load().fmskf_select
+        if out is None:
+            cap = self.n if capacity is None else int(capacity)
+            robots = np.empty(cap, np.uint32)
+            reason = np.empty(cap, np.uint8)
+            cnt = C.c_uint64()
+            check(fn(self.h, C.byref(prm), robots.ctypes.data_as(C.c_void_p) if cap else None,
+                     reason.ctypes.data_as(C.c_void_p) if cap else None, cap, C.byref(cnt), MEM_HOST), "select")
+            got = min(cnt.value, cap)
+            return robots[:got], reason[:got], cnt.value
+        robots, reason = out[0], out[1]
+        if _is_torch(robots):
+            import torch
+            cnt = out[2] if len(out) > 2 else torch.zeros(1, dtype=torch.int64, device=robots.device)
+            for name, t, dt in (("robots", robots, "int32"), ("reason", reason, "uint8"), ("count", cnt, "int64")):
+                if t is not None and not (t.is_cuda and t.is_contiguous() and str(t.dtype) == "torch." + dt):
+                    raise TypeError(f"select: {name} must be a contiguous {dt} device tensor")
+            cap = int(robots.numel()) if capacity is None else int(capacity)
+            if cap > robots.numel() or (reason is not None and cap > reason.numel()) or cnt.numel() < 1:
+                raise ValueError("select: capacity above the length of the out tensors")
+            check(fn(self.h, C.byref(prm), C.c_void_p(robots.data_ptr()),
+                     C.c_void_p(reason.data_ptr()) if reason is not None else None, cap,
+                     C.c_void_p(cnt.data_ptr()), MEM_DEVICE), "select")
+            return robots, reason, cnt
+        for name, a, dt in (("robots", robots, np.uint32), ("reason", reason, np.uint8)):
+            if a is not None and not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous
+                                      and a.flags.writeable):
+                raise TypeError(f"select: {name} must be a writable C-contiguous {np.dtype(dt).name} numpy array")
+        cap = (0 if robots is None else robots.size) if capacity is None else int(capacity)
+        if (cap and robots is None) or (robots is not None and cap > robots.size) or \
+                (reason is not None and cap > reason.size):
+            raise ValueError("select: capacity above the length of the out arrays")
+        cnt = C.c_uint64()
+        check(fn(self.h, C.byref(prm), robots.ctypes.data_as(C.c_void_p) if robots is not None else None,
+                 reason.ctypes.data_as(C.c_void_p) if reason is not None else None, cap, C.byref(cnt), MEM_HOST),
+              "select")
+        return robots, reason, cnt.value
+
+    def _lo_rows(self):
+        rows = C.c_uint32()
+        check(load().fmskf_get_state_lo(self.h, None, C.byref(rows), MEM_HOST), "get_state_lo")
+        return rows.value
+
+    def _robot_list(self, a, robots, what):
+        """(pointer, count) of a robot list: a uint32 numpy array (host) or an int32 device tensor"""
+        if _is_torch(robots) and robots.is_cuda:
+            if str(robots.dtype) != "torch.int32" or robots.dim() != 1:
+                raise TypeError(f"{what}: a device robot list must be a 1-d int32 tensor")
+            return a.ptr(robots), int(robots.numel())
+        robots = np.ascontiguousarray(robots)
+        if robots.ndim != 1 or robots.dtype.kind not in "iu":
+            raise TypeError(f"{what}: robots must be a 1-d integer array")
+        if robots.size and (robots.min() < 0 or robots.max() > 0xFFFFFFFF):
+            raise ValueError(f"{what}: robot index out of the uint32 range")
+        return a.ptr(robots, np.uint32), int(robots.size)
+
+    def get_state_subset(self, robots):
+        """fmskf_get_state_subset: (x [n, count], P [n(n+1)/2, count], lo [rows, count] or None
+        when the model keeps no low parts) of the listed robots -- strictly ascending; a uint32
+        numpy array (numpy results) or an int32 device tensor (torch device results, asynchronous
+        on the handle's stream)."""
+        a = _Args()
+        pr, count = self._robot_list(a, robots, "get_state_subset")
+        rows = self._lo_rows()
+        if a.mem == MEM_DEVICE:
+            import torch
+            mk = lambda r: torch.empty((r, count), dtype=torch.float32, device=robots.device)
+        else:
+            mk = lambda r: np.empty((r, count), np.float32)
+        x, P, lo = mk(self.nx), mk(self.np_), (mk(rows) if rows else None)
+        check(load().fmskf_get_state_subset(self.h, pr, count, a.ptr(x), a.ptr(P),
+                                            a.ptr(lo) if lo is not None else None, a.mem), "get_state_subset")
+        return x, P, lo
+
+    def get_state_subset_into(self, robots, x=None, P=None, lo=None):
+        """fmskf_get_state_subset into the caller's arrays ([rows, count] float32, in the list's
+        memory space; None skips an array): the form a graph capture takes"""
+        a = _Args()
+        pr, count = self._robot_list(a, robots, "get_state_subset")
+        ps = self._subset_planes(a, count, x, P, lo, "get_state_subset")
+        check(load().fmskf_get_state_subset(self.h, pr, count, *ps, a.mem), "get_state_subset")
+
+    def _subset_planes(self, a, count, x, P, lo, what):
+        out = []
+        for name, v, rows in (("x", x, self.nx), ("P", P, self.np_), ("lo", lo, None)):
+            if v is not None:
+                if _is_torch(v) and v.is_cuda and str(v.dtype) != "torch.float32":
+                    raise TypeError(f"{what}: {name} must be float32")
+                if len(v.shape) != 2 or v.shape[1] != count or (rows is not None and v.shape[0] != rows):
+                    raise ValueError(f"{what}: {name} has shape {tuple(v.shape)}, want [{rows or 'rows'}, {count}]")
+            out.append(a.ptr(v, np.float32) if v is not None else None)
+        rows = self._lo_rows() if lo is not None else 0
+        if rows and lo.shape[0] != rows:  # a model without low rows: the library refuses lo
+            raise ValueError(f"{what}: lo has {lo.shape[0]} rows, the model keeps {rows}")
+        return out
+
+    def set_state_subset(self, robots, x=None, P=None, lo=None):
+        """fmskf_set_state_subset: overwrite the listed robots' state with the columns of x
+        [n, count], P [n(n+1)/2, count], lo [rows, count] (any may be None), leaving every other
+        robot alone.  A given x restarts the heading low part, with CFG_COMP_POS a given x or P the
+        position low parts, unless lo is given.  The list and the arrays are all numpy (host) or
+        all torch device tensors (asynchronous; the form a graph capture takes)."""
+        a = _Args()
+        pr, count = self._robot_list(a, robots, "set_state_subset")
+        ps = self._subset_planes(a, count, x, P, lo, "set_state_subset")
+        check(load().fmskf_set_state_subset(self.h, pr, count, *ps, a.mem), "set_state_subset")
 
     # ------------------------------------------------------------------ ticks
     def _inputs(self, kw, n_ticks=1, stride=None):

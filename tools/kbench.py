@@ -53,6 +53,10 @@ def main():
                     help="KF6 / EKF9: time the absolute pose-fix pass (fmskf_correct_pose) alone, by kernel time as "
                          "--ktime does, with this share of the robots listed (1: every robot, 0.03125: one in 32)")
     ap.add_argument("--fix-m", type=int, choices=[2, 3], default=3, help="--pose-fix: 3 = with the heading")
+    ap.add_argument("--select", choices=["all", "pos_var", "nonfinite", "subset"], default=None,
+                    help="KF6 / EKF9: time fmskf_select (a POS_VAR-only select with 0.1 %%, 3 %% and 100 %% of the robots "
+                         "selected; a NONFINITE select with 0.1 %% planted) and the subset get / set of listed robots "
+                         "(densities 1, 1/32, 1/1024) with device pointers, one JSON line per row")
     ap.add_argument("--comm", action="store_true",
                     help="--op ens_async: a world-1 RCCL communicator on the handle (fmskf_comm_init)")
     args = ap.parse_args()
@@ -135,6 +139,8 @@ def main():
         preps = [e.prepare(valid=vm[r], **kws[r]) for r in range(R)]
     if args.pose_fix is not None:
         return bench_pose_fix(args, e, n, preps, dev)
+    if args.select is not None:
+        return bench_select(args, e, n, preps, dev, st)
     if args.host:
         return bench_host(args, e, n, yaw, gz, rpm)
     if args.op in ("pipeline", "pipeline_graph", "isr", "isr_graph", "isr_can", "can_isr", "isr_can_graph",
@@ -346,6 +352,107 @@ def bench_pose_fix(args, e, n, preps, dev):
                       "line_MB_per_pass_est": robot.size * (rows * 128 * 2 * lines_per_fix_row + 16) / 1e6,
                       "ignored": e.get_counters()[3],
                       "finite": bool(np.isfinite(x).all() and np.isfinite(P).all())}), flush=True)
+
+
+def bench_select(args, e, n, preps, dev, st):
+    """fmskf_select and the subset get / set with device pointers: device time per call
+    (fmskf_set_timing: HIP events around the call's launches -- a select is four, a subset call one)
+    and stream time per call (HIP events around `--ticks` back-to-back calls, the host's launch rate
+    included).  Algorithmic
+    bytes of a select: the rows its criteria load per robot (POS_VAR 8, NONFINITE 108 / 216), the
+    flag byte written and read again, a count per 256 robots written and read twice, 4 + 1 per
+    selected robot; of a subset call: the listed robots' x and P rows once each way plus the list."""
+    import numpy as np
+    import torch
+    R = len(preps)
+    for k in range(20):
+        e.tick_prepared(preps[k % R])
+    rows = e.nx + e.np_
+    robots = torch.empty(n, dtype=torch.int32, device=dev)
+    reason = torch.empty(n, dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def timed(fn):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        ev0.record(st)
+        for _ in range(args.ticks):
+            fn()
+        ev1.record(st)
+        torch.cuda.synchronize()
+        stream_us = ev0.elapsed_time(ev1) * 1e3 / args.ticks
+        e.set_timing(True)
+        for _ in range(args.ticks):
+            fn()
+        tot, cnt = e.kernel_time_total()
+        e.set_timing(False)
+        return tot * 1e3 / max(cnt, 1), stream_us
+
+    def listed(share, seed):
+        """an ascending device list of about share * n robots, scattered"""
+        if share >= 1.0:
+            return torch.arange(n, dtype=torch.int32, device=dev)
+        g = torch.Generator(device=dev)
+        g.manual_seed(seed)
+        return torch.nonzero(torch.rand(n, generator=g, device=dev) < share).flatten().to(torch.int32)
+
+    def row(**kw):
+        print(json.dumps({"model": args.model, "n": n, **kw}), flush=True)
+
+    scan = 3 * 4 / 256.0  # the block counts: written, read by the chunk sums and by the emit
+    if args.select in ("all", "pos_var"):
+        for share in (0.001, 0.03, 1.0):
+            e.reset()
+            for k in range(20):
+                e.tick_prepared(preps[k % R])
+            lst = listed(share, 11)
+            x, P, _ = e.get_state_subset(lst)
+            P[0] = 1e6
+            e.set_state_subset(lst, P=P)
+            us, sus = timed(lambda: e.select(pos_var_min=1e3, out=(robots, reason, count)))
+            k = int(count.item())
+            assert k == lst.numel() and torch.equal(robots[:k], lst)
+            b = n * (8 + 2 + scan) + 5 * k
+            row(op="select_pos_var", share=share, selected=k, us_per_call=us, stream_us_per_call=sus, algo_bytes=b,
+                algo_GBps=b / us / 1e3)
+    if args.select in ("all", "nonfinite"):
+        e.reset()
+        for k in range(20):
+            e.tick_prepared(preps[k % R])
+        lst = listed(0.001, 12)
+        x, _, _ = e.get_state_subset(lst)
+        x[e.nx - 1] = float("nan")
+        e.set_state_subset(lst, x=x)
+        us, sus = timed(lambda: e.select(nonfinite=True, out=(robots, reason, count)))
+        k = int(count.item())
+        assert k == lst.numel() and torch.equal(robots[:k], lst)
+        b = n * (rows * 4 + 2 + scan) + 5 * k
+        row(op="select_nonfinite", share=0.001, selected=k, us_per_call=us, stream_us_per_call=sus, algo_bytes=b,
+            algo_GBps=b / us / 1e3)
+        us, sus = timed(lambda: e.select(nonfinite=True, capacity=0, out=(robots, reason, count)))
+        b = n * (rows * 4 + 1 + 2 * 4 / 256.0)
+        row(op="select_nonfinite_count_only", selected=int(count.item()), us_per_call=us, stream_us_per_call=sus,
+            algo_bytes=b, algo_GBps=b / us / 1e3)
+    if args.select in ("all", "subset"):
+        e.reset()
+        for k in range(20):
+            e.tick_prepared(preps[k % R])
+        for stride in (1, 32, 1024):
+            lst = torch.arange(0, n, stride, dtype=torch.int32, device=dev)
+            c = int(lst.numel())
+            x = torch.empty((e.nx, c), dtype=torch.float32, device=dev)
+            P = torch.empty((e.np_, c), dtype=torch.float32, device=dev)
+            get_us, get_sus = timed(lambda: e.get_state_subset_into(lst, x, P))
+            set_us, set_sus = timed(lambda: e.set_state_subset(lst, x=x, P=P))
+            b = c * (rows * 4 * 2 + 4)
+            # line traffic on the state side: a wave's 64 robots at stride s touch min(64, 2 s) 128-byte lines a row
+            line = c * (rows * (128 * min(1.0, stride / 32.0) + 4) + 4)
+            row(op="state_subset", density=1.0 / stride, count=c, get_us=get_us, set_us=set_us,
+                get_stream_us=get_sus, set_stream_us=set_sus, algo_bytes=b,
+                line_bytes_est=line, get_line_GBps=line / get_us / 1e3, set_line_GBps=line / set_us / 1e3)
+        assert e.get_counters()[4] == 0
 
 
 def bench_host(args, e, n, yaw, gz, rpm):
