@@ -176,6 +176,7 @@ __global__ __launch_bounds__(kBlock) void k_isr_kf6(KfArgs<MdKF6, Kf6Params> a, 
   float *stab = wtab[O::LIBM ? 0 : threadIdx.x >> 6];
   WaveTable<O::LIBM> tv(a.in.sintab);
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
+  const Kf6Old old = kf6_keep_old(P);
   Kf6In m = kf6_load_in<O>(a.in, n, 0, ic);
   CtrlLane<true, CPC> L;
   L.load(c, ic);
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(kBlock) void k_isr_kf6(KfArgs<MdKF6, Kf6Params> a, 
   Kf6Gate<O, false> gt;  // no gated form: the gated handle takes the three-kernel ISR
   kf6_tick1<O>(m, stab, a.prm, x, P, lo, gt);
   if (live) {
-    kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
+    kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
     kf6_store_lo<O>(a.prm.lo, i, lo);
   }
   nan_guard(x, P, a.counters, live);

@@ -4,7 +4,8 @@
 // One robot per lane, x (6) and packed P (21) in VGPRs; a tick = measurement frontend
 // (yaw, gyro z, 4 wheel rpm -> z, the reference's deg2rad / mecanum FK / rotation,
 // VD_vehicle_controller.cpp:21-51) + LDL^T-form update + F P F^T + Q predict, one read and
-// one write of every state byte: 232 algorithmic bytes per instance-tick.
+// one write of every state byte: 232 algorithmic bytes per instance-tick (the write of the
+// planes in kKf6SkipMask, kf6_lane.hpp, is issued only where a lane's value changed).
 //
 // Memory-path design (MI355X_MICROARCH.md: s_waitcnt vmcnt is in-order, so any load issued
 // after the state loads makes every later wait cover them):
@@ -64,6 +65,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   Kf6GateOf<O, A> gt;
   Kf6In ma, mb;
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
+  const Kf6Old old = kf6_keep_old(P);  // as loaded: compared after the launch's last tick
   kf6_load_lo<O>(a.prm.lo, ic, lo);
   gt.load(gate_dev(aa), ic, n);
   if (O::UPD) ma = kf6_load_in<O>(a.in, n, 0, ic);
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
     kf6_tick1<O>(mb, stab, a.prm, x, P, lo, gt);
   }
   if (live) {
-    kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
+    kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
     kf6_store_lo<O>(a.prm.lo, i, lo);
     gt.store(gate_dev(aa), i, n);
   }
@@ -107,12 +109,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   Kf6Lo<O> lo;
   Kf6Gate<O, false> gt;
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
+  const Kf6Old old = kf6_keep_old(P);
   kf6_load_lo<O>(a.prm.lo, ic, lo);
   if (O::UPD) m = kf6_load_in<O>(a.in, n, 0, ic);
   tv.store(stab);
   kf6_tick1<O>(m, stab, a.prm, x, P, lo, gt);
   if (live) {
-    kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
+    kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
     kf6_store_lo<O>(a.prm.lo, i, lo);
   }
   nan_guard(x, P, a.counters, live);
@@ -157,12 +160,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
     Kf6Lo<O> lo;
     Kf6GateOf<O, A> gt;
     kf6_load_state<O>(a.x, a.P, a.pitch, live ? i : last, x, P);
+    const Kf6Old old = kf6_keep_old(P);
     kf6_load_lo<O>(a.prm.lo, live ? i : last, lo);
     gt.load(gate_dev(aa), live ? i : last, n);
     if (r == 0) tv.store(stab);
     kf6_tick1<O>(m[r], stab, a.prm, x, P, lo, gt);
     if (live) {
-      kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P);
+      kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
       kf6_store_lo<O>(a.prm.lo, i, lo);
       gt.store(gate_dev(aa), i, n);
     }

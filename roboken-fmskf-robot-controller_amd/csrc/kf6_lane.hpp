@@ -146,30 +146,70 @@ __device__ __forceinline__ void kf6_load_state(const float *xg, const float *Pg,
   }
 }
 
+// Write-back only where changed.  KF6 has constant F and H and rotates the wheel velocity by the
+// MEASURED yaw, so neither update nor predict couples the heading pair (theta, omega) with the
+// translation quad (px, py, vx, vy): with a block-diagonal Q, R and P0 (the default tuning) their
+// cross-covariance planes stay what they were, tick after tick.  The planes in kKf6SkipMask (bit k
+// = packed plane k) are stored only by the lanes whose bit pattern differs from the loaded one, so
+// a wave in which no lane changed issues no store and dirties no line; memory holds the same bytes
+// either way, for any Q, R and state.  Bits, not floats: -0.0 -> +0.0 and a NaN are written.
+// Structural planes only (not those that merely converge under one tuning), so a tick costs the
+// same at every step.  The cross planes are 3, 4, 8, 12, 15, 16, 18, 19 (P20 P21 P32 P42 P50 P51
+// P53 P54); the mask is their position half, P20 P21 P50 P51 (profiles/kf6_skip_store_ab.json).
+#ifndef FMSKF_KF6_SKIP_MASK
+#define FMSKF_KF6_SKIP_MASK ((1u << 3) | (1u << 4) | (1u << 15) | (1u << 16))
+#endif
+constexpr uint32_t kKf6SkipMask = FMSKF_KF6_SKIP_MASK;
+static_assert((kKf6SkipMask >> 21) == 0 && (kKf6SkipMask & (uint32_t)kKf6CPM) == 0,
+              "packed P planes only, none of the compensated ones");
+constexpr int kKf6SkipN = __builtin_popcount(kKf6SkipMask);
+constexpr bool kf6_skip(int k) { return ((kKf6SkipMask >> k) & 1u) != 0; }
+constexpr int kf6_skip_slot(int k) { return __builtin_popcount(kKf6SkipMask & ((1u << k) - 1u)); }
+// the loaded bit patterns of the masked planes
+struct Kf6Old {
+  uint32_t v[kKf6SkipN ? kKf6SkipN : 1];
+};
+__device__ __forceinline__ Kf6Old kf6_keep_old(const float (&P)[21]) {
+  Kf6Old o;
+#pragma unroll
+  for (int k = 0; k < 21; k++)
+    if (kf6_skip(k)) o.v[kf6_skip_slot(k)] = __builtin_bit_cast(uint32_t, P[k]);
+  return o;
+}
+// plane k of P (k a constant once the callers' loops are unrolled): every lane, or for a masked
+// plane the lanes whose bits changed
+template <int SP>
+__device__ __forceinline__ void kf6_st_p(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, int k, float v,
+                                         const Kf6Old &old) {
+  if (kf6_skip(k) && __builtin_bit_cast(uint32_t, v) == old.v[kf6_skip_slot(k)]) return;
+  st_f32<SP>(r, voff, soff, v);
+}
+
 template <class O>
 __device__ __forceinline__ void kf6_store_state(float *xg, float *Pg, uint64_t pp, uint32_t i,
-                                                const float (&x)[6], const float (&P)[21]) {
+                                                const float (&x)[6], const float (&P)[21], const Kf6Old &old) {
+  constexpr int SP = st_pol(O::CP);
   if constexpr (FMSKF_KF6_TILED) {
     constexpr uint32_t W = tile_w<float>();
     const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
     const uint32_t c = (i - tl * W) * 4u;
     const auto rx = rsrc(xg + (uint64_t)tl * (6 * W), 6 * W * 4), rp = rsrc(Pg + (uint64_t)tl * (21 * W), 21 * W * 4);
 #pragma unroll
-    for (int k = 0; k < 6; k++) st_f32<st_pol(O::CP)>(rx, c, k * W * 4, x[k]);
+    for (int k = 0; k < 6; k++) st_f32<SP>(rx, c, k * W * 4, x[k]);
 #pragma unroll
-    for (int k = 0; k < 21; k++) st_f32<st_pol(O::CP)>(rp, c, k * W * 4, P[k]);
+    for (int k = 0; k < 21; k++) kf6_st_p<SP>(rp, c, k * W * 4, k, P[k], old);
   } else if constexpr (O::SMALL) {
     const auto rx = rsrc(xg, pp * 24), rp = rsrc(Pg, pp * 84);
     const uint32_t ps = (uint32_t)pp * 4u;
 #pragma unroll
-    for (int k = 0; k < 6; k++) st_f32<st_pol(O::CP)>(rx, i * 4u, k * ps, x[k]);
+    for (int k = 0; k < 6; k++) st_f32<SP>(rx, i * 4u, k * ps, x[k]);
 #pragma unroll
-    for (int k = 0; k < 21; k++) st_f32<st_pol(O::CP)>(rp, i * 4u, k * ps, P[k]);
+    for (int k = 0; k < 21; k++) kf6_st_p<SP>(rp, i * 4u, k * ps, k, P[k], old);
   } else {
 #pragma unroll
-    for (int k = 0; k < 6; k++) st_f32<st_pol(O::CP)>(rsrc(xg + k * pp, pp * 4), i * 4u, 0, x[k]);
+    for (int k = 0; k < 6; k++) st_f32<SP>(rsrc(xg + k * pp, pp * 4), i * 4u, 0, x[k]);
 #pragma unroll
-    for (int k = 0; k < 21; k++) st_f32<st_pol(O::CP)>(rsrc(Pg + k * pp, pp * 4), i * 4u, 0, P[k]);
+    for (int k = 0; k < 21; k++) kf6_st_p<SP>(rsrc(Pg + k * pp, pp * 4), i * 4u, 0, k, P[k], old);
   }
 }
 
@@ -217,21 +257,22 @@ template <class O>
 struct Kf6Gate<O, true> {
   static constexpr bool ON = true;
   static_assert(O::UPD && !O::COMP && !O::ENS, "the gate: plain state, no fused ensemble record");
-  uint32_t hb, li, word, max_run;
+  uint32_t hb, li, word, word0, max_run;
   float nis_max, nis;
   bool seen;
   __device__ __forceinline__ void load(const GateDev &g, uint32_t ic, uint64_t n) {
     hb = gate_chunk(ic);
     li = ic - hb;
-    word = ld_chunk<uint32_t, O::CP>(g.word, hb, n, li);
+    word = word0 = ld_chunk<uint32_t, O::CP>(g.word, hb, n, li);
     max_run = g.max_run;
     nis_max = g.nis_max;
     nis = 0.f;
     seen = false;
   }
-  // a live lane's clamped index is its own, so the slot of the load is the slot of the store
+  // a live lane's clamped index is its own, so the slot of the load is the slot of the store;
+  // the word (an accepting robot's stays what it was) is written only where it changed
   __device__ __forceinline__ void store(const GateDev &g, uint32_t, uint64_t n) const {
-    st_chunk<uint32_t, st_pol(O::CP)>(g.word, hb, n, li, word);
+    if (word != word0) st_chunk<uint32_t, st_pol(O::CP)>(g.word, hb, n, li, word);
     if (seen) st_chunk<float, st_pol(O::CP)>(g.nis, hb, n, li, nis);
   }
 };

@@ -57,6 +57,9 @@ def main():
                     help="KF6 / EKF9: time fmskf_select (a POS_VAR-only select with 0.1 %%, 3 %% and 100 %% of the robots "
                          "selected; a NONFINITE select with 0.1 %% planted) and the subset get / set of listed robots "
                          "(densities 1, 1/32, 1/1024) with device pointers, one JSON line per row")
+    ap.add_argument("--dense-qr", action="store_true",
+                    help="KF6: Q and R with every off-diagonal at correlation 0.3 (the heading and the translation "
+                         "blocks coupled, so every covariance plane changes on every tick)")
     ap.add_argument("--comm", action="store_true",
                     help="--op ens_async: a world-1 RCCL communicator on the handle (fmskf_comm_init)")
     args = ap.parse_args()
@@ -67,8 +70,17 @@ def main():
 
     dev = torch.device("cuda", 0)
     n, R = args.n, max(args.ring, args.many)  # tick_many reads `many` ticks of the ring
+    qr = {}
+    if args.dense_qr:
+        def dense(packed, m):
+            a = np.array(packed[: m * (m + 1) // 2], np.float64)
+            d = np.sqrt([a[i * (i + 1) // 2 + i] for i in range(m)])
+            return np.array([a[i * (i + 1) // 2 + j] if i == j else 0.3 * d[i] * d[j]
+                             for i in range(m) for j in range(i + 1)], np.float32)
+        cfg = fmskf.default_config("kf6", n)
+        qr = dict(q=dense(cfg.q, 6), r=dense(cfg.r, 4))
     e = fmskf.Engine(args.model, n, trig=fmskf.TRIG_LIBM if args.trig == "libm" else fmskf.TRIG_TABLE512,
-                     flags=fmskf.CFG_COMP_POS if args.comp else 0)
+                     flags=fmskf.CFG_COMP_POS if args.comp else 0, **qr)
     if args.comp:
         BYTES["kf6"], BYTES["ekf9"] = 272, 488
     if args.gate is not None:  # + the gate word read and written, the NIS written

@@ -834,6 +834,37 @@ __global__ void k_fill_rand(uint32_t *p, uint64_t words, uint32_t seed) {
   }
 }
 
+// the tiled KF6 pattern (k_tiled_pol) with conditional write-back: every row is loaded; the rows
+// in SKIP (bit k = row k, x rows 0-5, packed P plane p at row 6 + p) are stored only by the lanes
+// whose value changed (a bit compare that depends on the loads and the record), the others by
+// every lane.  chg = 0: nothing changes, so no SKIP row is stored by any wave; chg = 1: every
+// value changes, so the compares are paid and every store is issued
+template <int T, int LAUX, int SAUX, uint32_t SKIP>
+__global__ __launch_bounds__(256) void k_tiled_skip(uint32_t *st, const uint4 *raw, uint64_t n, uint32_t chg) {
+  const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  const uint64_t b = (uint64_t)blockIdx.x;
+  uint32_t *base = st + (b / (T / 256)) * (27ull * T) + (b % (T / 256)) * 256;
+  const auto r = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(26u * T * 4 + 1024), 0x00020000);
+  const uint32_t vo = threadIdx.x * 4u;
+  uint32_t s[27];
+#pragma unroll
+  for (int k = 0; k < 27; k++) s[k] = __builtin_amdgcn_raw_buffer_load_b32(r, vo, k * T * 4, LAUX);
+  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(raw) + v);
+  const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+  const uint32_t m = ((q0 ^ q1 ^ q2 ^ q3) | 1u) & chg;
+#pragma unroll
+  for (int k = 0; k < 27; k++) {
+    const uint32_t t = s[k] ^ m;
+    if ((SKIP >> k) & 1u) {
+      if (t != s[k]) __builtin_amdgcn_raw_buffer_store_b32(t, r, vo, k * T * 4, SAUX);
+    } else {
+      __builtin_amdgcn_raw_buffer_store_b32(t, r, vo, k * T * 4, SAUX);
+    }
+  }
+}
+
 int main(int argc, char **argv) {
   const int lg = argc > 1 ? atoi(argv[1]) : 20;
   const uint64_t n = 1ull << lg;
@@ -1316,6 +1347,60 @@ int main(int argc, char **argv) {
         tm("persist_nopipe_blocks_per_cu", bpc, [&] { k_tiled_persist<54, 864, false><<<gp, 256>>>(sb, ib, n, 0.f); });
       }
     }
+    return 0;
+  }
+  if (argc > 3 && argv[3][0] == 's') {
+    // membench LG 1 skip: the tiled KF6 pattern with the write-back of k P planes left out where
+    // unchanged (k_tiled_skip), k = 0, 4, 8, 13: does time follow the written bytes?  Plain loads
+    // and sc1 stores while the state fits the Infinity Cache (LG <= 20), non-temporal past it, as
+    // the tick kernels choose.  Records from a ring of ticks; three interleaved passes.
+    hipEvent_t f0, f1;
+    CK(hipEventCreate(&f0));
+    CK(hipEventCreate(&f1));
+    const bool nt = 108 * n > (256ull << 20);
+    const int ring = nt ? 4 : 64;
+    const uint64_t tiles = (n + 2047) / 2048;
+    uint32_t *sb;
+    uint4 *ib;
+    CK(hipMalloc(&sb, tiles * 27 * 2048 * 4));
+    CK(hipMalloc(&ib, (size_t)ring * n * 16));
+    k_fill_rand<<<4096, 256>>>(sb, tiles * 27 * 2048, 7);
+    k_fill_rand<<<4096, 256>>>((uint32_t *)ib, (uint64_t)ring * n * 4, 8);
+    CK(hipDeviceSynchronize());
+    const unsigned g = (unsigned)((n + 255) / 256);
+    int tick = 0;
+    auto tm = [&](const char *name, int planes, uint32_t chg, auto launch) {
+      for (int w = 0; w < 5; w++) launch(ib + (size_t)(tick++ % ring) * n, chg);
+      CK(hipEventRecord(f0));
+      for (int it = 0; it < 100; it++) launch(ib + (size_t)(tick++ % ring) * n, chg);
+      CK(hipEventRecord(f1));
+      CK(hipEventSynchronize(f1));
+      float ms = 0;
+      CK(hipEventElapsedTime(&ms, f0, f1));
+      const double us = ms * 1e3 / 100;
+      printf("{\"n\": %llu, \"kernel\": \"%s\", \"nt\": %d, \"masked_planes\": %d, \"all_change\": %u, \"us\": %.2f, "
+             "\"bytes_moved\": %d}\n",
+             (unsigned long long)n, name, (int)nt, planes, chg, us, 232 - (chg ? 0 : 4 * planes));
+    };
+    // packed P plane p is row 6 + p: B = {3, 4, 15, 16}, A = B + {8, 12, 18, 19}, 13 = A + {0, 2, 6, 9, 14}
+    constexpr uint32_t MB = (1u << 9) | (1u << 10) | (1u << 21) | (1u << 22);
+    constexpr uint32_t MA = MB | (1u << 14) | (1u << 18) | (1u << 24) | (1u << 25);
+    constexpr uint32_t M13 = MA | (1u << 6) | (1u << 8) | (1u << 12) | (1u << 15) | (1u << 20);
+#define SKIPRUN(MASK, K, CHG, NAME)                                                                      \
+  tm(NAME, K, CHG, [&](const uint4 *in, uint32_t c) {                                                    \
+    if (nt) k_tiled_skip<2048, 2, 2, MASK><<<g, 256>>>(sb, in, n, c);                                    \
+    else k_tiled_skip<2048, 0, 16, MASK><<<g, 256>>>(sb, in, n, c);                                      \
+  })
+    for (int rep = 0; rep < 3; rep++) {
+      SKIPRUN(0u, 0, 0u, "skip0");
+      SKIPRUN(MB, 4, 0u, "skip4");
+      SKIPRUN(MA, 8, 0u, "skip8");
+      SKIPRUN(M13, 13, 0u, "skip13");
+      SKIPRUN(0u, 0, 1u, "skip0_all_change");  // the control of the two below: no compares
+      SKIPRUN(MB, 4, 1u, "skip4_all_change");
+      SKIPRUN(MA, 8, 1u, "skip8_all_change");
+    }
+#undef SKIPRUN
     return 0;
   }
   if (argc > 3 && argv[3][0] == 'p') {
