@@ -532,7 +532,27 @@ int fmskf_get_motors(fmskf_handle h, int16_t *angle, int16_t *rpm, int16_t *curr
  * the last two angles), flt_SpeedRadPS.  Any pointer may be NULL. */
 int fmskf_get_motor_status(fmskf_handle h, int16_t *microsec_id, int16_t *angle, int16_t *rpm,
                            int16_t *curr, float *dlt_out_angle_rad, float *speed_radps, uint32_t mem);
-/* counters: [0] = instances whose state went non-finite (NaN/Inf guard); [1] = calls of
+/* counters: [0] = instances whose state went non-finite (NaN/Inf guard), counted per launch:
+ * every tick kernel of KF6, EKF9 and KF12D (fmskf_tick, fmskf_correct, fmskf_predict,
+ * fmskf_tick_many, fmskf_tick_ensemble / fmskf_tick_ensemble_begin, fmskf_isr_tick,
+ * fmskf_isr_tick_can; gated or not) adds one for every robot of the fleet whose x or packed P is
+ * not finite as the launch stores it.  A robot that stays bad is therefore counted again by every
+ * later launch: [0] is a count of robot-launches, not of distinct robots (fmskf_select with
+ * FMSKF_SEL_NONFINITE names the robots).  fmskf_tick_many over T ticks is one launch and counts a
+ * robot once, T single ticks count it T times.  The guard tests the sum of the robot's x and P
+ * elements, so a state of finite elements whose sum overflows counts too (a sum of at most 90
+ * elements: only with elements near the top of the format's range).  The hidden low parts
+ * (fmskf_get_state_lo) are not inspected.  fmskf_correct_pose counts the fixes it applied only,
+ * those whose robot it stores non-finite, and visits no robot that is not listed.  A listed robot
+ * with a NaN in what the fix's NIS reads (its position block: px, py, P00, P10, P11, their low
+ * parts, with a heading fix theta and its covariance entries too) has a NaN NIS, is
+ * FMSKF_GATE_REJECTED and is not counted.  One that is non-finite only elsewhere has a finite NIS,
+ * and so may one with an Inf and no NaN in its position block (P00 = +Inf gives 1 / S = 0): where
+ * nis_max admits the NIS the fix is applied, the robot stored and counted.  (After a tick's
+ * update a bad robot is as a rule NaN in every element.)  FMSKF_MODEL_RS is never counted (its
+ * kernels have no guard).  fmskf_set_state, fmskf_set_state_subset and the readouts leave [0]
+ * alone, fmskf_reset zeroes it, fmskf_save_state / fmskf_load_state keep and restore it.
+ * [1] = calls of
  * fmskf_isr_tick_can that ran the CAN RX as a kernel of its own before the ISR (a caller rpm /
  * angle sums / KF6 records, CAN buffers not 16-byte (frames) / 8-byte (stamps) aligned, or a
  * regime where the ISR is not one kernel); [2] = ISRs (fmskf_isr_tick or fmskf_isr_tick_can)
