@@ -127,11 +127,11 @@ void ck_layout(const fmskf_ctx *h, CkHeader *hd) {
   hd->pitch = h->s.pitch;
   hd->tile = h->s.tile;
   hd->elem = h->d.elem;
-  hd->ctrl_tile = FMSKF_CTRL_TILED ? tile_w_elem(4) : 0;
+  hd->ctrl_tile = tile_w_elem(4);
   hd->m_pitch = plane_pitch(h->s.n);
   hd->layout = (h->s.prev_sum ? kCkPrevRows : 0u) | kCkSumSplit | kCkImuYg | kCkRpmPrev | kCkImuRow;
   const uint64_t w = tile_w_elem(4);
-  hd->ctrl_pitch = FMSKF_CTRL_TILED ? std::max(h->s.pitch, (h->s.n + w - 1) / w * w) : h->s.pitch;
+  hd->ctrl_pitch = std::max(h->s.pitch, (h->s.n + w - 1) / w * w);
 }
 
 // 64-bit multiply-xor hash of a byte stream in 8-byte words (the tail zero-padded); the value

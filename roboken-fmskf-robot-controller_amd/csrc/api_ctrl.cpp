@@ -90,7 +90,7 @@ void ensure_ctrl(fmskf_ctx *h) {
   c.n = h->s.n;
   // tiled interpolator / FF_PI_D arrays cover ceil(N / W) whole tiles (ctrl_lane.hpp Planes)
   const uint64_t w = tile_w_elem(4);
-  c.pitch = FMSKF_CTRL_TILED ? std::max(h->s.pitch, (c.n + w - 1) / w * w) : h->s.pitch;
+  c.pitch = std::max(h->s.pitch, (c.n + w - 1) / w * w);
   c.ax = h->alloc<float>((size_t)3 * kAxF * c.pitch);
   c.pid = h->alloc<float>((size_t)4 * kPidF * c.pitch);
   c.vel_tgt = h->alloc<float>((size_t)3 * c.pitch);
@@ -346,17 +346,13 @@ int fmskf_get_ctrl(fmskf_handle h, float *vel_tgt, int16_t *curr_raw, float *whe
     const size_t row = c.n * 4, pb = c.pitch * 4;
     copy_planes_out(h, vel_tgt, c.vel_tgt, row, pb, 3, mem);
     copy_out(h, curr_raw, c.curr, c.n * 8, mem);
-    // wheel w's field k is plane w*kPidF + k: planes of one field are kPidF planes apart
-    const float *pid = c.pid;
-    size_t ppb = pb;
-    if (FMSKF_CTRL_TILED && (wheel_tgt || wheel_ctrl)) {  // dense [4 * kPidF][N] copy first
+    if (wheel_tgt || wheel_ctrl) {  // the pid planes are tiled: a dense [4 * kPidF][N] copy first
       float *dense = (float *)h->stage_for((size_t)4 * kPidF * row);
       launch_check(launch_untile(c.pid, dense, 4 * kPidF, c.n, 4, h->stream), "untile pid");
-      pid = dense;
-      ppb = row;
+      // wheel w's field k is plane w*kPidF + k: planes of one field are kPidF planes apart
+      copy_planes_out(h, wheel_tgt, dense + 4 * c.n, row, row * kPidF, 4, mem);
+      copy_planes_out(h, wheel_ctrl, dense + 5 * c.n, row, row * kPidF, 4, mem);
     }
-    copy_planes_out(h, wheel_tgt, pid + 4 * (ppb / 4), row, ppb * kPidF, 4, mem);
-    copy_planes_out(h, wheel_ctrl, pid + 5 * (ppb / 4), row, ppb * kPidF, 4, mem);
     finish_out(h, mem);
   });
 }

@@ -197,7 +197,7 @@ void do_reset(fmskf_ctx *h) {
   hipStream_t st = h->stream;
   const uint64_t pp = s.pitch;
   hip_check(hipMemsetAsync(s.x, 0, (size_t)d.nx * pp * d.elem, st), "reset x");
-  if (d.m > 0 && s.tile) {  // tiled P: every row filled with its P0 entry in one pass
+  if (d.m > 0) {  // the models with a covariance are tiled: every row filled with its P0 entry in one pass
     std::vector<uint64_t> bits(np);
     for (uint32_t k = 0; k < np; k++) {
       const double v = h->cfg.p0[k];
@@ -211,25 +211,6 @@ void do_reset(fmskf_ctx *h) {
       }
     }
     launch_check(launch_tiled_fill(s.P, np, n, bits.data(), d.elem, st), "reset P0");
-  } else if (d.m > 0) {
-    hip_check(hipMemsetAsync(s.P, 0, (size_t)np * pp * d.elem, st), "reset P");
-    for (uint32_t i = 0; i < d.nx; i++) {
-      for (uint32_t j = 0; j <= i; j++) {
-        const double v = h->cfg.p0[i * (i + 1) / 2 + j];
-        if (v == 0.0) continue;
-        const size_t k = i * (i + 1) / 2 + j;
-        if (d.elem == 4) {
-          float f = (float)v;
-          uint32_t bits;
-          memcpy(&bits, &f, 4);
-          hip_check(hipMemsetD32Async((hipDeviceptr_t)((float *)s.P + k * pp), bits, n, st), "reset P0");
-        } else {
-          uint64_t bits;
-          memcpy(&bits, &v, 8);
-          launch_check(launch_fill64((double *)s.P + k * pp, bits, n, st), "reset P0");
-        }
-      }
-    }
   }
   if (s.prev_sum) hip_check(hipMemsetAsync(s.prev_sum, 0, 4 * pp * 8, st), "reset prev");
   if (s.thlo) hip_check(hipMemsetAsync(s.thlo, 0, n * 4, st), "reset heading low part");
@@ -509,9 +490,8 @@ int fmskf_create(const fmskf_config *cfg, fmskf_handle *out) {
       s.n = n;
       s.model = cfg->model;
       const uint32_t np = d.nx * (d.nx + 1) / 2;
-      s.tile = (FMSKF_TILED && (cfg->model == FMSKF_MODEL_EKF9 || cfg->model == FMSKF_MODEL_KF12D)) ||
-                       (FMSKF_KF6_TILED && cfg->model == FMSKF_MODEL_KF6)
-                   ? tile_w_elem(d.elem) : 0;
+      // the KF6, EKF9 and KF12D state is tiled, the RS state planar (fmskf_internal.hpp st_at)
+      s.tile = cfg->model == FMSKF_MODEL_RS ? 0 : tile_w_elem(d.elem);
       // a tiled array's rows x pitch elements cover ceil(N / tile) whole tiles
       s.pitch = s.tile ? std::max(plane_pitch(n), (n + s.tile - 1) / s.tile * s.tile) : plane_pitch(n);
       s.x = h->alloc<char>((size_t)d.nx * s.pitch * d.elem);

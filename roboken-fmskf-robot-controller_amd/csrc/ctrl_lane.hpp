@@ -100,68 +100,46 @@ __device__ __forceinline__ int16_t curr_to_raw(float amp, int dir, int lim) {
   return (t > lim) ? (int16_t)lim : ((t < -lim) ? (int16_t)-lim : t);
 }
 
-// Plane access for the control state.  Tiled (FMSKF_CTRL_TILED, the default): the interpolator
-// and FF_PI_D arrays are [N/W][planes][W] with W = tile_w<float>() (fmskf_internal.hpp st_at),
-// one scalar descriptor over robot i's tile (wave-uniform: a wave's robots lie in one
-// 256-robot chunk) and a scalar offset per plane.  Planar: SMALL (every array within a 4 GiB
-// buffer window) uses buffer descriptors with a 32-bit lane offset and a scalar per-plane
-// offset; otherwise plain 64-bit global addressing.
-template <bool SMALL, int CP = 0>
+// Plane access for the control state: the interpolator and FF_PI_D arrays are tiled,
+// [N/W][planes][W] with W = tile_w<float>() (fmskf_internal.hpp st_at).  One scalar descriptor
+// over robot i's tile (wave-uniform: a wave's robots lie in one 256-robot chunk), a 32-bit lane
+// offset and a scalar offset per plane.
+template <int CP = 0>
 struct Planes {
   static constexpr uint32_t W = tile_w<float>();
   __amdgpu_buffer_rsrc_t r;
-  float *base;
-  uint64_t pp;
   uint32_t vo;
-  __device__ __forceinline__ Planes(float *b, uint64_t pitch, int nplanes, uint32_t i)
-      : base(b), pp(pitch), vo(i * 4u) {
-    if constexpr (FMSKF_CTRL_TILED) {
-      const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
-      r = rsrc(b + (uint64_t)tl * nplanes * W, (uint64_t)nplanes * W * 4);
-      vo = (i - tl * W) * 4u;
-    } else if constexpr (SMALL) {
-      r = rsrc(b, pitch * 4 * nplanes);
-    }
+  __device__ __forceinline__ Planes(float *b, int nplanes, uint32_t i) {
+    const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
+    r = rsrc(b + (uint64_t)tl * nplanes * W, (uint64_t)nplanes * W * 4);
+    vo = (i - tl * W) * 4u;
   }
-  __device__ __forceinline__ float ld(int plane, uint32_t i) const {
-    if constexpr (FMSKF_CTRL_TILED)
-      return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, plane * W * 4, CP));
-    else if constexpr (SMALL)
-      return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                           r, vo, (uint32_t)(plane * pp * 4), CP));
-    else
-      return base[plane * pp + i];
+  __device__ __forceinline__ float ld(int plane) const {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, plane * W * 4, CP));
   }
-  __device__ __forceinline__ void st(int plane, uint32_t i, float v) const {
-    if constexpr (FMSKF_CTRL_TILED)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, vo, plane * W * 4,
-                                            st_pol(CP));
-    else if constexpr (SMALL)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, vo,
-                                            (uint32_t)(plane * pp * 4), st_pol(CP));
-    else
-      base[plane * pp + i] = v;
+  __device__ __forceinline__ void st(int plane, float v) const {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), r, vo, plane * W * 4, st_pol(CP));
   }
 };
 
 // One robot's control step, split in its load phase (every load issued up front: vmcnt
 // retires in order) and its compute + store phase, so a fused kernel can issue the loads of
 // several steps before computing any of them.
-template <bool SMALL, int CP = 0>
+template <int CP = 0>
 struct CtrlLane {
   uint8_t on;
   Interp ax[3];
   float pv[4][4];
 
   __device__ __forceinline__ void load(const CtrlDev &c, uint32_t i) {
-    const Planes<SMALL, CP> AX(c.ax, c.pitch, 3 * kAxF, i), PD(c.pid, c.pitch, 4 * kPidF, i);
+    const Planes<CP> AX(c.ax, 3 * kAxF, i), PD(c.pid, 4 * kPidF, i);
     on = c.power[i];
     // every interpolator field but acl_now, which update() writes before any use (round 6: 12 B
     // less per robot; only set_target_params reads it, as acl_ini)
 #pragma unroll
     for (int a = 0; a < 3; a++)
 #pragma unroll
-      for (int k = 0; k < kAxF; k++) ax[a].f[k] = k == IV_A ? 0.0f : AX.ld(a * kAxF + k, i);
+      for (int k = 0; k < kAxF; k++) ax[a].f[k] = k == IV_A ? 0.0f : AX.ld(a * kAxF + k);
     // now_val from the rpm the last step ran on (CtrlDev::rpm_prev), the other loop fields from
     // their planes
     const uint2 rp = reinterpret_cast<const uint2 *>(c.rpm_prev)[i];
@@ -171,7 +149,7 @@ struct CtrlLane {
     for (int w = 0; w < 4; w++) {
       pv[w][PD_VAL] = rpm_to_mvel(r[w]) * 36.0f;
 #pragma unroll
-      for (int k = PD_INTEG; k < 4; k++) pv[w][k] = PD.ld(w * kPidF + k, i);
+      for (int k = PD_INTEG; k < 4; k++) pv[w][k] = PD.ld(w * kPidF + k);
     }
   }
 
@@ -179,7 +157,7 @@ struct CtrlLane {
   // raw current targets (also stored to c.curr).
   __device__ __forceinline__ uint2 step(const CtrlDev &c, const CtrlPrm &p, uint32_t i, uint2 rw) {
     const uint64_t pp = c.pitch;
-    const Planes<SMALL, CP> AX(c.ax, pp, 3 * kAxF, i), PD(c.pid, pp, 4 * kPidF, i);
+    const Planes<CP> AX(c.ax, 3 * kAxF, i), PD(c.pid, 4 * kPidF, i);
     float v[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) v[a] = interp_update(ax[a], p.ts);
@@ -224,15 +202,15 @@ struct CtrlLane {
     // the interpolator fields update() changes; after a reset (power off) all of them
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-      AX.st(a * kAxF + IV_DT, i, ax[a].f[IV_DT]);
-      AX.st(a * kAxF + IV_V, i, ax[a].f[IV_V]);
-      AX.st(a * kAxF + IV_A, i, ax[a].f[IV_A]);
+      AX.st(a * kAxF + IV_DT, ax[a].f[IV_DT]);
+      AX.st(a * kAxF + IV_V, ax[a].f[IV_V]);
+      AX.st(a * kAxF + IV_A, ax[a].f[IV_A]);
     }
     if (!on) {
 #pragma unroll
       for (int a = 0; a < 3; a++)
 #pragma unroll
-        for (int k = 0; k < IV_DT; k++) AX.st(a * kAxF + k, i, 0.0f);
+        for (int k = 0; k < IV_DT; k++) AX.st(a * kAxF + k, 0.0f);
     }
     // the loop state the next step reads; now_tgt, now_ctrl and vel_tgt only where they cannot
     // be formed later from that state (power off: the reset erased the interpolators' output) or
@@ -240,13 +218,13 @@ struct CtrlLane {
 #pragma unroll
     for (int w = 0; w < 4; w++)
 #pragma unroll
-      for (int k = PD_INTEG; k < PD_TGT; k++) PD.st(w * kPidF + k, i, po[w][k]);
+      for (int k = PD_INTEG; k < PD_TGT; k++) PD.st(w * kPidF + k, po[w][k]);
     reinterpret_cast<uint2 *>(c.rpm_prev)[i] = on ? rw : make_uint2(0u, 0u);  // now_val's rpm
     if (p.store_derived) {
 #pragma unroll
       for (int w = 0; w < 4; w++) {
-        PD.st(w * kPidF + PD_TGT, i, po[w][PD_TGT]);
-        PD.st(w * kPidF + PD_CTRL, i, po[w][PD_CTRL]);
+        PD.st(w * kPidF + PD_TGT, po[w][PD_TGT]);
+        PD.st(w * kPidF + PD_CTRL, po[w][PD_CTRL]);
       }
     }
     if (!on || p.store_derived) {
@@ -266,20 +244,19 @@ struct CtrlLane {
 // operations as the step give the same bits; with it off the step reset everything, stored
 // vel_tgt itself, and the loops' target and output are 0.  Valid while the power flags and the
 // parameters are those of that step (the host materialises before set_power; p: the step's)
-template <bool SMALL>
 __device__ __forceinline__ void ctrl_derive_lane(const CtrlDev &c, const CtrlPrm &p, uint32_t i) {
-  const Planes<SMALL> AX(c.ax, c.pitch, 3 * kAxF, i), PD(c.pid, c.pitch, 4 * kPidF, i);
+  const Planes<> AX(c.ax, 3 * kAxF, i), PD(c.pid, 4 * kPidF, i);
   if (!c.power[i]) {
 #pragma unroll
     for (int w = 0; w < 4; w++) {
-      PD.st(w * kPidF + PD_TGT, i, 0.0f);
-      PD.st(w * kPidF + PD_CTRL, i, 0.0f);
+      PD.st(w * kPidF + PD_TGT, 0.0f);
+      PD.st(w * kPidF + PD_CTRL, 0.0f);
     }
     return;
   }
   float v[3], mt[4];
 #pragma unroll
-  for (int a = 0; a < 3; a++) v[a] = AX.ld(a * kAxF + IV_V, i);
+  for (int a = 0; a < 3; a++) v[a] = AX.ld(a * kAxF + IV_V);
   float pv[4][3];
   const uint2 rp = reinterpret_cast<const uint2 *>(c.rpm_prev)[i];
   const int16_t r[4] = {(int16_t)(rp.x & 0xFFFFu), (int16_t)(rp.x >> 16), (int16_t)(rp.y & 0xFFFFu),
@@ -288,14 +265,14 @@ __device__ __forceinline__ void ctrl_derive_lane(const CtrlDev &c, const CtrlPrm
   for (int w = 0; w < 4; w++) {
     pv[w][PD_VAL] = rpm_to_mvel(r[w]) * 36.0f;  // now_val, as the step formed it
 #pragma unroll
-    for (int k = PD_INTEG; k < 3; k++) pv[w][k] = PD.ld(w * kPidF + k, i);  // PD_INTEG, PD_LY
+    for (int k = PD_INTEG; k < 3; k++) pv[w][k] = PD.ld(w * kPidF + k);  // PD_INTEG, PD_LY
   }
   vdir_to_mdir(v, mt);
 #pragma unroll
   for (int w = 0; w < 4; w++) {
     const float tgt = mt[w] * 36.0f;
-    PD.st(w * kPidF + PD_TGT, i, tgt);
-    PD.st(w * kPidF + PD_CTRL, i, ffpid_out(p, tgt, pv[w][PD_VAL], pv[w][PD_INTEG], pv[w][PD_LY]));
+    PD.st(w * kPidF + PD_TGT, tgt);
+    PD.st(w * kPidF + PD_CTRL, ffpid_out(p, tgt, pv[w][PD_VAL], pv[w][PD_INTEG], pv[w][PD_LY]));
   }
 #pragma unroll
   for (int a = 0; a < 3; a++) c.vel_tgt[a * c.pitch + i] = v[a];

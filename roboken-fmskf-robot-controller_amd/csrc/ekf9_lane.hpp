@@ -40,7 +40,6 @@ struct Ekf9Gate {
 template <int CP>
 struct Ekf9Gate<true, CP> {
   static constexpr bool ON = true;
-  static_assert(FMSKF_TILED, "the row gate: tiled state only");
   uint64_t word;
   float d2[6];
   bool seen;

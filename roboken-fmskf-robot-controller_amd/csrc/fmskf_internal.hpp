@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdlib>
 #include <cmath>
+#include <type_traits>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -25,16 +26,17 @@ enum : int { kSnapValid = 1, kSnapLatched = 2 };
 // instance i lives at [k * N + i] unless the comment says [N][k].
 struct DevState {
   uint64_t n = 0;
-  // plane pitch (elements) of x and P: plane k of instance i at [k * pitch + i].  Never a
-  // large power of two (see plane_pitch): power-of-two plane strides alias in the
-  // memory-side cache / channel hash and cost ~20% of bandwidth at N = 2^20 (membench).
+  // elements per row of x and P (rows x pitch is the allocation).  Planar (RS): plane k of
+  // instance i at [k * pitch + i]; never a large power of two (see plane_pitch): power-of-two
+  // plane strides alias in the memory-side cache / channel hash and cost ~20% of bandwidth at
+  // N = 2^20 (membench).  Tiled: at least N rounded up to the tile width.
   uint64_t pitch = 0;
-  // 0: x / P are planar [rows][pitch]; else the tile width W: tiled [ceil(N/W)][rows][W]
-  // (EKF9, KF12D; tile_w)
+  // the tile width W of x / P, tiled [ceil(N/W)][rows][W] (KF6, EKF9, KF12D; tile_w), or 0: the
+  // RS state, planar [rows][pitch]
   uint32_t tile = 0;
   uint32_t model = 0;
-  // estimator state: x [nx][pitch], P [np][pitch] (element type float, or double for KF12D);
-  // RS: x = (px, py, th, vx, vy, vth) floats
+  // estimator state: x (nx rows) and P (np rows) of `pitch` elements each, laid out as `tile`
+  // says (element type float, or double for KF12D); RS: x = (px, py, th, vx, vy, vth) floats
   void *x = nullptr;
   void *P = nullptr;
   int64_t *prev_sum = nullptr;  // RS: s64_rawAngleSumPrev, 64-robot tiles of wheel pairs (lane_rs.hpp rs_prev_at)
@@ -303,7 +305,8 @@ inline bool ekf9_r_diagonal(const float *r21) {
 }
 
 // Vehicle control state, allocated on first use of the control entry
-// points.  Planes at the state pitch:
+// points.  ax and pid are tiled like the fp32 estimator state (st_at with tile_w<float>(), their
+// rows x pitch allocation covering whole tiles); vel_tgt is planar at the pitch:
 //   ax  [3 axes][12][pitch]: VelInterpConstJerk page (vel_tgt, acl_max, jerk_p, jerk_m, dt1,
 //                            dt2, dt3, vel_ini, acl_ini, dt) + vel_now, acl_now
 //   pid [4 wheels][6][pitch]: FF_PI_D (now_val == prev_val, Integ, LPF now_Y, LPF prev_X,
@@ -351,9 +354,10 @@ inline uint64_t plane_pitch(uint64_t n) { return ((n + 511) / 512) * 512 + 256; 
 // W = 256 309-313 us, 512 290-291, 1024 282-284, 2048 279-281, 4096 282-284; KF12D's 90 fp64
 // rows at 2^20 with 1280 fp64 FMAs: 256 269-270, 1024 268-269, 2048 263-265, 4096 259-260.
 // (Against planar planes the 256-wide tile already measured 374.6 -> 353.6 us for EKF9.)  The
-// KF6 state (FMSKF_KF6_TILED) and the control state's interpolator / FF_PI_D arrays
-// (FMSKF_CTRL_TILED) use the fp32 width too; the RS state stays planar.  The allocation
-// (rows x pitch, pitch >= N rounded up to W) always covers ceil(N / W) tiles.
+// KF6 state and the control state's interpolator / FF_PI_D arrays use the fp32 width too.  The
+// layout is fixed: only the RS state is planar (DevState::tile == 0), and the planar builds of
+// the other arrays are gone.  The allocation (rows x pitch, pitch >= N rounded up to W) always
+// covers ceil(N / W) tiles.
 template <typename T>
 constexpr uint32_t tile_w() { return sizeof(T) == 8 ? 4096u : 2048u; }  // fp64 (KF12D) / fp32
 inline uint32_t tile_w_elem(uint32_t elem) { return elem == 8 ? 4096u : 2048u; }
@@ -409,19 +413,20 @@ inline uint64_t est_state_bytes(const DevState &s) {
     return v_ >= 0 ? (unsigned)v_ : ((HBM) ? (unsigned)(DFLT) : 0u); \
   }())
 
-#ifndef FMSKF_TILED
-#define FMSKF_TILED 1
-#endif
-// the KF6 state tiled like EKF9's (2048 robots per tile row) instead of planar planes at the
-// padded pitch; 0 builds the planar layout (A/B)
-#ifndef FMSKF_KF6_TILED
-#define FMSKF_KF6_TILED 1
-#endif
-// the control state's interpolator and FF_PI_D arrays tiled the same way (ctrl_lane.hpp
-// Planes); 0 builds them planar at the state pitch (A/B)
-#ifndef FMSKF_CTRL_TILED
-#define FMSKF_CTRL_TILED 1
-#endif
+// Run-time bools as compile-time ones: with_bools(f, a, b) calls the generic lambda f with a
+// std::bool_constant per bool, f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a launcher
+// names its kernel once (k<A(), B()>) instead of once per combination.  Every combination of
+// f's body is instantiated: exclude the ones that must not exist with `if constexpr`.
+template <class F>
+inline auto with_bools(F &&f) { return f(); }
+template <class F, class... Bs>
+inline auto with_bools(F &&f, bool b, Bs... bs) {
+  return b ? with_bools([&](auto... k) { return f(std::true_type{}, k...); }, bs...)
+           : with_bools([&](auto... k) { return f(std::false_type{}, k...); }, bs...);
+}
+
+// element k of instance i in a state array: tiled (tile = W, see tile_w above) or, for the RS
+// state (tile = 0), planar at the plane pitch
 __host__ __device__ inline uint64_t st_at(uint32_t tile, uint64_t pitch, uint32_t rows, uint32_t k,
                                           uint64_t i) {
   return tile ? ((i / tile) * rows + k) * tile + i % tile : k * pitch + i;
@@ -523,7 +528,6 @@ int launch_imu_data(const DevState &s, float *out, hipStream_t st);
 int launch_vehicle_info(const DevState &s, const float *readout, void *out, const uint8_t *floor,
                         const float *cam_pitch, const uint32_t *fault, hipStream_t st);
 // readout helpers
-int launch_fill64(void *p, uint64_t bits, uint64_t count, hipStream_t st);
 // tiled state arrays (kernels_misc.hip): fill row k with bits[k] (elem 4 or 8 bytes); convert
 // between the tiled array (rows x N) and dense [rows][N] planes
 int launch_tiled_fill(void *base, uint32_t rows, uint64_t n, const uint64_t *bits, uint32_t elem,

@@ -27,18 +27,15 @@ namespace fmskf {
 __global__ __launch_bounds__(kBlock) void k_ctrl_set_target(CtrlDev c, const float *vel,
                                                             const float *acl, const float *jrk,
                                                             const uint8_t *mask) {
-  const uint64_t n = c.n, pp = c.pitch;
+  const uint64_t n = c.n;
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   if (mask && !mask[i]) return;
 #pragma unroll
   for (int a = 0; a < 3; a++) {
     Interp s;
-    // plane a * kAxF + k of robot i (tiled or planar, ctrl_lane.hpp Planes)
-    auto at = [&](int k) -> uint64_t {
-      const uint32_t pl = (uint32_t)(a * kAxF + k);
-      return FMSKF_CTRL_TILED ? st_at(tile_w<float>(), 0, 3 * kAxF, pl, i) : pl * pp + i;
-    };
+    // plane a * kAxF + k of robot i (tiled, ctrl_lane.hpp Planes)
+    auto at = [&](int k) -> uint64_t { return st_at(tile_w<float>(), 0, 3 * kAxF, (uint32_t)(a * kAxF + k), i); };
 #pragma unroll
     for (int k = 0; k < kAxF; k++) s.f[k] = c.ax[at(k)];
     interp_set(s, vel[a * n + i], acl[a * n + i], jrk[a * n + i]);
@@ -50,13 +47,13 @@ __global__ __launch_bounds__(kBlock) void k_ctrl_set_target(CtrlDev c, const flo
 // The per-tick control step.  rpm [N][4] int16 (MOTOR_IF_M2006::Status.s16_rawSpeedRpm).
 // rstride: robot i's four rpm at rpm + 4 * rstride * i (1: [N][4] planes; 2: the rpm field of
 // 16-byte fmskf_kf6_record's)
-template <bool SMALL, int CP = 0>
+template <int CP = 0>
 __global__ __launch_bounds__(kBlock) void k_ctrl_step(CtrlDev c, CtrlPrm p, const int16_t *rpm,
                                                       uint32_t rstride) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= (uint32_t)c.n) return;
   const uint2 rw = reinterpret_cast<const uint2 *>(rpm)[(uint64_t)i * rstride];
-  CtrlLane<SMALL, CP> L;
+  CtrlLane<CP> L;
   L.load(c, i);
   L.step(c, p, i, rw);
 }
@@ -89,7 +86,7 @@ struct IsrRsArgs {
 // takes those and the prev planes are neither read nor written (64 B per robot-tick: 685 -> 621 B);
 // the host copies the sums into the prev planes before anything else reads them
 // (rs_prev_materialize).  Mrad is the same int64 difference, so the result is bit-identical.
-template <bool LIBM, bool SMALL, int CP = 0, bool CAN = false, bool CNT = false, bool PS = false>
+template <bool LIBM, int CP = 0, bool CAN = false, bool CNT = false, bool PS = false>
 __global__ __launch_bounds__(kBlock) void k_isr_rs(IsrRsArgs a, CtrlDev c, CtrlPrm p, CanArgs can) {
   static_assert(CAN || !PS, "the previous sums come from the CAN lane");
   const uint64_t n = c.n, pp = a.pitch;
@@ -118,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_isr_rs(IsrRsArgs a, CtrlDev c, CtrlP
       for (int w = 0; w < 4; w++) sum[w] = a.angle_sum[w * a.sum_pitch + i];
     }
   }
-  CtrlLane<SMALL, CP> L;
+  CtrlLane<CP> L;
   L.load(c, i);
   if constexpr (CAN) {
     rw = cl.step(can, true);
@@ -178,7 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_isr_kf6(KfArgs<MdKF6, Kf6Params> a, 
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
   const Kf6Old old = kf6_keep_old(P);
   Kf6In m = kf6_load_in<O>(a.in, n, 0, ic);
-  CtrlLane<true, CPC> L;
+  CtrlLane<CPC> L;
   L.load(c, ic);
   tv.store(stab);
   Kf6Lo<O> lo;  // O::COMP: the position low parts (FMSKF_CFG_COMP_POS)
@@ -285,29 +282,26 @@ int launch_ctrl_set_target(const CtrlDev &c, const float *vel, const float *acl,
 int launch_ctrl_step(const CtrlDev &c, const CtrlPrm &p, const int16_t *rpm, uint32_t rstride,
                      hipStream_t st) {
   if (c.n == 0) return 0;
+  // the window test: a regime boundary inherited from the planar layout (the tiled planes need none)
   if (c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull && state_nt(ctrl_state_bytes(c)))
     // 3 blocks per CU (48 KiB dynamic LDS): 2^22 239.4-239.5 -> 235.9-237.0 us
-    k_ctrl_step<true, kStateNT><<<grid1(c.n), kBlock, FMSKF_LDS_CAP("FMSKF_CTRL_LDS", true, 48u * 1024u), st>>>(c, p, rpm, rstride);
-  else if (c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull)
-    k_ctrl_step<true><<<grid1(c.n), kBlock, 0, st>>>(c, p, rpm, rstride);
+    k_ctrl_step<kStateNT><<<grid1(c.n), kBlock, FMSKF_LDS_CAP("FMSKF_CTRL_LDS", true, 48u * 1024u), st>>>(c, p, rpm, rstride);
   else
-    k_ctrl_step<false><<<grid1(c.n), kBlock, 0, st>>>(c, p, rpm, rstride);
+    k_ctrl_step<><<<grid1(c.n), kBlock, 0, st>>>(c, p, rpm, rstride);
   return (int)hipGetLastError();
 }
 
 // the step outputs nothing reads back, formed when a reader needs them (ctrl_lane.hpp
 // ctrl_derive_lane; host: fmskf_ctx::ctrl_derived_stale)
-template <bool SMALL>
 __global__ __launch_bounds__(kBlock) void k_ctrl_derive(CtrlDev c, CtrlPrm p) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   if (i >= (uint32_t)c.n) return;
-  ctrl_derive_lane<SMALL>(c, p, i);
+  ctrl_derive_lane(c, p, i);
 }
 
 int launch_ctrl_derive(const CtrlDev &c, const CtrlPrm &p, hipStream_t st) {
   if (c.n == 0) return 0;
-  if (c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull) k_ctrl_derive<true><<<grid1(c.n), kBlock, 0, st>>>(c, p);
-  else k_ctrl_derive<false><<<grid1(c.n), kBlock, 0, st>>>(c, p);
+  k_ctrl_derive<<<grid1(c.n), kBlock, 0, st>>>(c, p);
   return (int)hipGetLastError();
 }
 
@@ -317,20 +311,13 @@ static int isr_rs_l(const DevState &s, const TickIn &in, bool libm, const CtrlDe
   if (c.n == 0) return 0;
   const IsrRsArgs a{s.pitch, (float *)s.x, s.prev_sum, in.yaw_deg, in.rpm, in.angle_sum, in.sum_pitch,
                     in.msum_lo, in.msum_hi, in.sintab, frames, in.imu_words & 1u};
-  const bool small = c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull;
-  const bool nt = small && state_nt(ctrl_state_bytes(c) + s.n * 56);
-  if (nt) {
-    // 3 blocks per CU (48 KiB dynamic LDS): 2^20 75.7-76.5 -> 73.9 us (two passes)
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u);
-    if (libm) k_isr_rs<true, true, kStateNT, CAN, CNT, PS><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, can);
-    else k_isr_rs<false, true, kStateNT, CAN, CNT, PS><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, can);
-  } else if (libm) {
-    if (small) k_isr_rs<true, true, 0, CAN, CNT, PS><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, can);
-    else k_isr_rs<true, false, 0, CAN, CNT, PS><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, can);
-  } else {
-    if (small) k_isr_rs<false, true, 0, CAN, CNT, PS><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, can);
-    else k_isr_rs<false, false, 0, CAN, CNT, PS><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, can);
-  }
+  // the window test: a regime boundary inherited from the planar layout (the tiled planes need none)
+  const bool nt = c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull && state_nt(ctrl_state_bytes(c) + s.n * 56);
+  // 3 blocks per CU (48 KiB dynamic LDS): 2^20 75.7-76.5 -> 73.9 us (two passes)
+  const unsigned lds = nt ? FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u) : 0u;
+  with_bools([&](auto LIBM, auto NT) {
+    k_isr_rs<LIBM(), NT() ? kStateNT : 0, CAN, CNT, PS><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, can);
+  }, libm, nt);
   return (int)hipGetLastError();
 }
 
@@ -370,21 +357,15 @@ static int isr_kf6_v(const KfArgs<MdKF6, Kf6Params> &a, const CtrlDev &c, const 
 template <bool COMP>
 static int isr_kf6_c(const KfArgs<MdKF6, Kf6Params> &a, const CtrlDev &c, const CtrlPrm &p, uint8_t *frames, bool nt,
                      hipStream_t st, bool libm, bool valid, bool rec, const CanArgs *can) {
-  if (libm) {
-    if (valid) return rec ? isr_kf6_v<true, true, true, COMP>(a, c, p, frames, nt, st, can)
-                          : isr_kf6_v<true, true, false, COMP>(a, c, p, frames, nt, st, can);
-    return rec ? isr_kf6_v<true, false, true, COMP>(a, c, p, frames, nt, st, can)
-               : isr_kf6_v<true, false, false, COMP>(a, c, p, frames, nt, st, can);
-  }
-  if (valid) return rec ? isr_kf6_v<false, true, true, COMP>(a, c, p, frames, nt, st, can)
-                        : isr_kf6_v<false, true, false, COMP>(a, c, p, frames, nt, st, can);
-  return rec ? isr_kf6_v<false, false, true, COMP>(a, c, p, frames, nt, st, can)
-             : isr_kf6_v<false, false, false, COMP>(a, c, p, frames, nt, st, can);
+  return with_bools([&](auto LIBM, auto VALID, auto REC) {
+    return isr_kf6_v<LIBM(), VALID(), REC(), COMP>(a, c, p, frames, nt, st, can);
+  }, libm, valid, rec);
 }
 
 static int isr_kf6_l(const DevState &s, const TickIn &in, const Kf6Params &kp, bool libm, const CtrlDev &c,
                      const CtrlPrm &p, uint8_t *frames, hipStream_t st, const CanArgs *can) {
   if (c.n == 0) return 0;
+  // both window tests: regime boundaries inherited from the planar layout (the tiled arrays need none)
   const bool small_state = s.pitch * 84 < 0xFFFFFFFFull;
   const bool small_ctrl = c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull;
   // the tick kernel alone streams its state non-temporal past the cache: keep that regime on

@@ -141,7 +141,7 @@ static void launch_fix_m(const FixArgs &a, bool nt, bool big, hipStream_t st) {
 }
 
 int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st) {
-  if (!FMSKF_TILED || !FMSKF_KF6_TILED || s.tile != tile_w<float>()) return (int)hipErrorNotSupported;
+  if (s.tile != tile_w<float>()) return (int)hipErrorNotSupported;
   if (!f.fixes || !f.count || !f.ignored || (f.m != 2 && f.m != 3)) return (int)hipErrorInvalidValue;
   const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
   if ((!ekf && s.model != FMSKF_MODEL_KF6) || (ekf && (comp || !s.thlo))) return (int)hipErrorNotSupported;

@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void k_ekf9(A aa) {
     for (int k = threadIdx.x; k < 513; k += kBlock) stab[k] = a.in.sintab[k];
     __syncthreads();
   }
-  const uint64_t n = a.n, pp = a.pitch;
+  const uint64_t n = a.n;
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool live = i < n;
   const uint64_t ic = live ? i : n - 1;
@@ -68,17 +68,10 @@ __global__ __launch_bounds__(kBlock) void k_ekf9(A aa) {
   float x[N], P[NP];
   const TileRows<float, N> tx(a.x, tile_slot(n));
   const TileRows<float, NP> tp(a.P, tile_slot(n));
-  if constexpr (FMSKF_TILED) {
 #pragma unroll
-    for (int k = 0; k < N; k++) x[k] = tx.ld(k);
+  for (int k = 0; k < N; k++) x[k] = tx.ld(k);
 #pragma unroll
-    for (int k = 0; k < NP; k++) P[k] = tp.ld(k);
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; k++) x[k] = a.x[k * pp + ic];
-#pragma unroll
-    for (int k = 0; k < NP; k++) P[k] = a.P[k * pp + ic];
-  }
+  for (int k = 0; k < NP; k++) P[k] = tp.ld(k);
   float lo = a.prm.thlo[ic];
   Ekf9Lo<COMP, 0> cl;
   cl.load(a.prm.clo, blockIdx.x, tile_slot(n));
@@ -103,17 +96,10 @@ __global__ __launch_bounds__(kBlock) void k_ekf9(A aa) {
     a.prm.thlo[i] = lo;
     cl.store(a.prm.clo, blockIdx.x, tile_slot(n));
     gt.store(gate_dev(aa), (uint64_t)blockIdx.x * kBlock, n, tile_slot(n));
-    if constexpr (FMSKF_TILED) {
 #pragma unroll
-      for (int k = 0; k < N; k++) tx.st(k, x[k]);
+    for (int k = 0; k < N; k++) tx.st(k, x[k]);
 #pragma unroll
-      for (int k = 0; k < NP; k++) tp.st(k, P[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < N; k++) a.x[k * pp + i] = x[k];
-#pragma unroll
-      for (int k = 0; k < NP; k++) a.P[k * pp + i] = P[k];
-    }
+    for (int k = 0; k < NP; k++) tp.st(k, P[k]);
   }
   nan_guard(x, P, a.counters, live);
 }
@@ -133,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void k_ekf9t(A aa) {
   }
   __shared__ float wtab[LIBM ? 1 : kBlock / 64][LIBM ? 1 : kWaveTab];
   float *stab = wtab[LIBM ? 0 : threadIdx.x >> 6];
-  const uint64_t n = a.n, pp = a.pitch;
+  const uint64_t n = a.n;
   const uint64_t i = (uint64_t)bid * kBlock + threadIdx.x;
   const bool live = i < n;
   const uint64_t ic = live ? i : n - 1;
@@ -142,17 +128,10 @@ __global__ __launch_bounds__(kBlock) void k_ekf9t(A aa) {
   const uint32_t sl = tile_slot(n, bid);
   const TileRows<float, N, CP> tx(a.x, bid, sl, 0);
   const TileRows<float, NP, CP> tp(a.P, bid, sl, 0);
-  if constexpr (FMSKF_TILED) {
 #pragma unroll
-    for (int k = 0; k < N; k++) x[k] = tx.ld(k);
+  for (int k = 0; k < N; k++) x[k] = tx.ld(k);
 #pragma unroll
-    for (int k = 0; k < NP; k++) P[k] = tp.ld(k);
-  } else {
-#pragma unroll
-    for (int k = 0; k < N; k++) x[k] = a.x[k * pp + ic];
-#pragma unroll
-    for (int k = 0; k < NP; k++) P[k] = a.P[k * pp + ic];
-  }
+  for (int k = 0; k < NP; k++) P[k] = tp.ld(k);
   const bool have = a.in.valid == nullptr || a.in.valid[ic];
   const uint4 raw = UPD ? ekf9_raw_at<false>(a.in.raw, ic) : make_uint4(0, 0, 0, 0);
   const uint64_t hb0 = (uint64_t)bid * kBlock;
@@ -167,17 +146,10 @@ __global__ __launch_bounds__(kBlock) void k_ekf9t(A aa) {
     st_chunk<float, st_pol(CP)>(a.prm.thlo, hb0, n, sl, lo);
     cl.store(a.prm.clo, bid, sl);
     gt.store(gate_dev(aa), hb0, n, sl);
-    if constexpr (FMSKF_TILED) {
 #pragma unroll
-      for (int k = 0; k < N; k++) tx.st(k, x[k]);
+    for (int k = 0; k < N; k++) tx.st(k, x[k]);
 #pragma unroll
-      for (int k = 0; k < NP; k++) tp.st(k, P[k]);
-    } else {
-#pragma unroll
-      for (int k = 0; k < N; k++) a.x[k * pp + i] = x[k];
-#pragma unroll
-      for (int k = 0; k < NP; k++) a.P[k * pp + i] = P[k];
-    }
+    for (int k = 0; k < NP; k++) tp.st(k, P[k]);
   }
   nan_guard(x, P, a.counters, live);
   if constexpr (ENS) {
@@ -230,7 +202,7 @@ __global__ __launch_bounds__(kBlock) void k_isr_ekf9(KfArgs<MdEKF9, Ekf9Params> 
   cl.load(a.prm.clo, bid, sl);
   uint2 rw;
   if constexpr (!CAN) rw = reinterpret_cast<const uint2 *>(rpm)[ic];
-  CtrlLane<true, CPC> L;
+  CtrlLane<CPC> L;
   L.load(c, (uint32_t)ic);
   tv.store(stab);
   if constexpr (CAN) rw = cl4.step(can, live);
@@ -345,15 +317,15 @@ __global__ __launch_bounds__(kBlock) void k_ekf9p(A aa) {
 template <bool SEQ, bool UPD, bool PRED>
 __global__ __launch_bounds__(kBlock) void k_kf12d(KfArgs<MdKF12D, Kf12dParams> a) {
   constexpr int N = 12, NP = 78, M = 8;
-  const uint64_t n = a.n, pp = a.pitch;
+  const uint64_t n = a.n;
   const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   double x[N], P[NP];
-  const uint32_t tl = FMSKF_TILED ? tile_w<double>() : 0;
+  constexpr uint32_t tl = tile_w<double>();
 #pragma unroll
-  for (int k = 0; k < N; k++) x[k] = a.x[st_at(tl, pp, N, k, i)];
+  for (int k = 0; k < N; k++) x[k] = a.x[st_at(tl, 0, N, k, i)];
 #pragma unroll
-  for (int k = 0; k < NP; k++) P[k] = a.P[st_at(tl, pp, NP, k, i)];
+  for (int k = 0; k < NP; k++) P[k] = a.P[st_at(tl, 0, NP, k, i)];
   const double dt = a.prm.dt;
   const auto fdt = [&](int, int) { return dt; };
   for (uint32_t t = 0; t < a.in.n_ticks; t++) {
@@ -390,9 +362,9 @@ __global__ __launch_bounds__(kBlock) void k_kf12d(KfArgs<MdKF12D, Kf12dParams> a
     }
   }
 #pragma unroll
-  for (int k = 0; k < N; k++) a.x[st_at(tl, pp, N, k, i)] = x[k];
+  for (int k = 0; k < N; k++) a.x[st_at(tl, 0, N, k, i)] = x[k];
 #pragma unroll
-  for (int k = 0; k < NP; k++) a.P[st_at(tl, pp, NP, k, i)] = P[k];
+  for (int k = 0; k < NP; k++) a.P[st_at(tl, 0, NP, k, i)] = P[k];
   nan_guard(x, P, a.counters);
 }
 
@@ -508,52 +480,37 @@ __device__ __forceinline__ void kf12d_predict_cov(double (&P)[78], double dt, co
   }
 }
 
-// Planes through buffer descriptors: a 32-bit lane offset per access and no 64-bit address
-// math.  SMALL: the 78 P planes fit one 4 GiB window (pitch < 6.8M), one descriptor per array
-// and a scalar plane offset; otherwise one descriptor per plane (n < 2^29 lanes of 8 bytes).
+// The block's chunk of its tile through scalar descriptors (TileRows): a 32-bit lane offset per
+// access and no 64-bit address math.
 // ENS: the record epilogue of fmskf_tick_ensemble; every lane then stays to the block
 // reduction (lanes past N tick instance N-1, a clamped index, and store nothing)
-template <bool BLK, bool UPD, bool PRED, bool SMALL, int CP = 0, bool ENS = false, bool SP = false>
+template <bool BLK, bool UPD, bool PRED, int CP = 0, bool ENS = false, bool SP = false>
 __global__ __launch_bounds__(kBlock) void k_kf12s(KfArgs<MdKF12D, Kf12dParams> a) {
   constexpr int N = 12, NP = 78, M = 8;
   uint32_t bid = blockIdx.x;  // the tick block (the carried fold blocks come first)
   if constexpr (ENS) {
     if (ens_fold_front<12>(a.in, bid)) return;
   }
-  const uint64_t n = a.n, pp = a.pitch;
+  const uint64_t n = a.n;
   const uint64_t i0 = (uint64_t)bid * kBlock + threadIdx.x;
   const bool live = i0 < n;
   if (!ENS && !live) return;
   const uint64_t i = live ? i0 : n - 1;
   double x[N], P[NP];
-  const auto rx = rsrc(a.x, pp * 8 * N), rp = rsrc(a.P, pp * 8 * NP);
-  const uint32_t vo = (uint32_t)i * 8u;
-  uint32_t ps = (uint32_t)pp * 8u;
-  auto ld = [&](__amdgpu_buffer_rsrc_t r, const double *base, int k) -> double {
-    if constexpr (SMALL) {
-      return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, vo, k * ps, 0));
-    } else {  // one descriptor per plane (scalar work only)
-      return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rsrc(base + k * pp, pp * 8),
-                                                                              vo, 0, 0));
-    }
-  };
-  auto st = [&](__amdgpu_buffer_rsrc_t r, double *base, int k, double v) {
-    if constexpr (SMALL) {
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, v), r, vo, k * ps, 0);
-    } else {
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u32_t, v), rsrc(base + k * pp, pp * 8),
-                                            vo, 0, 0);
-    }
-  };
-  // tiled layout (FMSKF_TILED): the block's chunk of its tile through a scalar descriptor (without ENS
-  // lanes past N returned above, so a lane's slot is its thread index)
+  // Left from the planar form, whose store offsets the fence after the tick loop kept from being
+  // held across it: an opaque scalar use of the pitch between the loop and the stores.  Nothing
+  // reads ps, but without the pair every k_kf12s compiles to other code (the pitch load and a
+  // shift go, the scalar registers and the placement of the store offsets change), and that has
+  // not been measured
+  uint32_t ps = (uint32_t)a.pitch * 8u;
+  // without ENS lanes past N returned above, so a lane's slot is its thread index
   const uint32_t slot = ENS ? tile_slot(n, bid) : threadIdx.x;
   const TileRows<double, N, CP> tx(a.x, bid, slot, 0);
   const TileRows<double, NP, CP> tp(a.P, bid, slot, 0);
 #pragma unroll
-  for (int k = 0; k < N; k++) x[k] = FMSKF_TILED ? tx.ld(k) : ld(rx, a.x, k);
+  for (int k = 0; k < N; k++) x[k] = tx.ld(k);
 #pragma unroll
-  for (int k = 0; k < NP; k++) P[k] = FMSKF_TILED ? tp.ld(k) : ld(rp, a.P, k);
+  for (int k = 0; k < NP; k++) P[k] = tp.ld(k);
   const double dt = a.prm.dt;
   for (uint32_t t = 0; t < a.in.n_ticks; t++) {
     if (UPD) {
@@ -576,18 +533,12 @@ __global__ __launch_bounds__(kBlock) void k_kf12s(KfArgs<MdKF12D, Kf12dParams> a
       kf12d_predict_cov<SP>(P, dt, a.prm.coef + 36);
     }
   }
-  asm volatile("" : "+s"(ps));  // the store offsets are recomputed here, not held from the loads
+  asm volatile("" : "+s"(ps));  // (see ps above)
   if (live) {
 #pragma unroll
-    for (int k = 0; k < N; k++) {
-      if constexpr (FMSKF_TILED) tx.st(k, x[k]);
-      else st(rx, a.x, k, x[k]);
-    }
+    for (int k = 0; k < N; k++) tx.st(k, x[k]);
 #pragma unroll
-    for (int k = 0; k < NP; k++) {
-      if constexpr (FMSKF_TILED) tp.st(k, P[k]);
-      else st(rp, a.P, k, P[k]);
-    }
+    for (int k = 0; k < NP; k++) tp.st(k, P[k]);
   }
   nan_guard(x, P, a.counters, live);
   if constexpr (ENS) {
@@ -643,7 +594,7 @@ static Ekf9Regime ekf9_regime(uint64_t n, uint64_t sb, bool libm, bool nt) {
   }();
   const int v = var == 2 || var == 4 ? var : (n * sb <= (256ull << 20) ? 2 : 4);
   // 64 KiB of dynamic LDS (2 blocks per CU): 2^20 71.2 -> 70.5-70.7 us (two passes)
-  if (FMSKF_TILED && !libm && v == 2) return {true, FMSKF_LDS_CAP("FMSKF_EKF9P_LDS", true, 64u * 1024u)};
+  if (!libm && v == 2) return {true, FMSKF_LDS_CAP("FMSKF_EKF9P_LDS", true, 64u * 1024u)};
   if (libm) return {false, 0u};
   // Past the Infinity Cache (non-temporal state) the occupancy is capped at 2 blocks per CU
   // with 64 KiB of dynamic LDS: fewer concurrent tile streams per HBM channel.  2^22:
@@ -687,33 +638,22 @@ static void launch_ekf9_l(const A &aa, uint64_t sb, bool upd, bool pred, bool nt
   }
 }
 
-template <bool SEQ, bool COMP>
-static int launch_ekf9_s(const Ekf9Args &a, const DevState &s, const TickIn &in, bool libm, bool upd, bool pred,
-                         bool nt, hipStream_t st, int *ens_nb) {
-  if (in.ens_blocks)
-    *ens_nb = libm ? launch_ekf9_ens<true, SEQ, COMP>(a, s, nt, st) : launch_ekf9_ens<false, SEQ, COMP>(a, s, nt, st);
-  else if (libm) launch_ekf9_l<true, SEQ, COMP>(a, COMP ? 240 : 220, upd, pred, nt, st);
-  else launch_ekf9_l<false, SEQ, COMP>(a, COMP ? 240 : 220, upd, pred, nt, st);
-  return (int)hipGetLastError();
-}
-
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
                 bool pred, hipStream_t st, int *ens_nb) {
   KfArgs<MdEKF9, Ekf9Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p};
   a.prm.thlo = s.thlo;
   a.prm.clo = s.xlo;  // FMSKF_CFG_COMP_POS
-  if (!s.thlo || (s.xlo && !FMSKF_TILED)) return (int)hipErrorInvalidValue;
-  const bool nt = FMSKF_TILED && state_nt(s.n * (s.xlo ? 60 : 55) * 4);
-  if ((in.ens_blocks && (!FMSKF_TILED || !ens_nb || !upd || !pred || in.n_ticks != 1)) ||
-      (in.fold_blocks && !in.ens_blocks))
+  if (!s.thlo) return (int)hipErrorInvalidValue;
+  const bool nt = state_nt(s.n * (s.xlo ? 60 : 55) * 4);
+  if ((in.ens_blocks && (!ens_nb || !upd || !pred || in.n_ticks != 1)) || (in.fold_blocks && !in.ens_blocks))
     return (int)hipErrorInvalidValue;
   // canonical update order (oracle orc_ekf9_tick): sequential scalar updates when R is
-  // diagonal, the joint LDL^T update otherwise
-  const bool diag = ekf9_r_diagonal(p.r);
-  if (s.xlo) return diag ? launch_ekf9_s<true, true>(a, s, in, libm, upd, pred, nt, st, ens_nb)
-                         : launch_ekf9_s<false, true>(a, s, in, libm, upd, pred, nt, st, ens_nb);
-  return diag ? launch_ekf9_s<true, false>(a, s, in, libm, upd, pred, nt, st, ens_nb)
-              : launch_ekf9_s<false, false>(a, s, in, libm, upd, pred, nt, st, ens_nb);
+  // diagonal (SEQ), the joint LDL^T update otherwise
+  with_bools([&](auto LIBM, auto SEQ, auto COMP) {
+    if (in.ens_blocks) *ens_nb = launch_ekf9_ens<LIBM(), SEQ(), COMP()>(a, s, nt, st);
+    else launch_ekf9_l<LIBM(), SEQ(), COMP()>(a, COMP() ? 240 : 220, upd, pred, nt, st);
+  }, libm, ekf9_r_diagonal(p.r), s.xlo != nullptr);
+  return (int)hipGetLastError();
 }
 
 // The row-gated handle (fmskf_set_row_gate): the same kernels on RowGateArgs through the same
@@ -722,7 +662,7 @@ int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool l
 // the gate.
 int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p, const RowGateDev &g,
                         bool libm, bool pred, hipStream_t st) {
-  if (!FMSKF_TILED || !s.tile || !s.thlo || s.xlo || in.ens_blocks || in.fold_blocks || !in.raw || !g.word ||
+  if (!s.tile || !s.thlo || s.xlo || in.ens_blocks || in.fold_blocks || !in.raw || !g.word ||
       !g.d2 || g.d2_pitch < s.n || !ekf9_r_diagonal(p.r))
     return (int)hipErrorInvalidValue;
   if (!pred && in.n_ticks != 1) return (int)hipErrorInvalidValue;
@@ -735,54 +675,28 @@ int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p
   return (int)hipGetLastError();
 }
 
-template <bool LIBM, bool SEQ, bool COMP, bool CAN, bool CNT>
-static int isr_ekf9_w(const KfArgs<MdEKF9, Ekf9Params> &a, const CtrlDev &c, const CtrlPrm &p, uint8_t *frames,
-                      const int16_t *rpm, bool nt, hipStream_t st, const CanArgs &can) {
-  const dim3 g = grid_for(c.n);
-  if (nt) {
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u);
-    k_isr_ekf9<LIBM, SEQ, kStateNT, COMP, CAN, CNT><<<g, kBlock, lds, st>>>(a, c, p, frames, rpm, can);
-  } else {
-    k_isr_ekf9<LIBM, SEQ, 0, COMP, CAN, CNT><<<g, kBlock, 0, st>>>(a, c, p, frames, rpm, can);
-  }
-  return (int)hipGetLastError();
-}
-
-template <bool LIBM, bool SEQ, bool COMP, bool CAN>
-static int isr_ekf9_v(const KfArgs<MdEKF9, Ekf9Params> &a, const CtrlDev &c, const CtrlPrm &p, uint8_t *frames,
-                      const int16_t *rpm, bool nt, hipStream_t st, const CanArgs &can) {
-  if constexpr (CAN) {
-    // the EKF9 state and the motor state together past the Infinity Cache: the motor state
-    // streams non-temporal and the EKF9 state stays resident
-    if (can_nt_flag(can)) return isr_ekf9_w<LIBM, SEQ, COMP, true, true>(a, c, p, frames, rpm, nt, st, can);
-  }
-  return isr_ekf9_w<LIBM, SEQ, COMP, CAN, false>(a, c, p, frames, rpm, nt, st, can);
-}
-
-template <bool SEQ, bool COMP, bool CAN>
-static int isr_ekf9_c(const KfArgs<MdEKF9, Ekf9Params> &a, const CtrlDev &c, const CtrlPrm &p, uint8_t *frames,
-                      const int16_t *rpm, bool nt, bool libm, hipStream_t st, const CanArgs &can) {
-  return libm ? isr_ekf9_v<true, SEQ, COMP, CAN>(a, c, p, frames, rpm, nt, st, can)
-              : isr_ekf9_v<false, SEQ, COMP, CAN>(a, c, p, frames, rpm, nt, st, can);
-}
-
 template <bool CAN>
 static int isr_ekf9_l(const DevState &s, const TickIn &in, const Ekf9Params &prm, bool libm, const CtrlDev &c,
                       const CtrlPrm &p, const int16_t *rpm, uint8_t *frames, hipStream_t st, const CanArgs &can) {
   if (c.n == 0) return 0;
   const uint64_t sb = s.xlo ? 240 : 220;  // state bytes per robot (+ the compensation rows)
-  if (!FMSKF_TILED || !s.thlo || in.n_ticks != 1 || !in.raw || (!CAN && !rpm) || state_nt(s.n * sb) ||
+  // the window test on the control planes: a regime boundary inherited from the planar layout
+  if (!s.thlo || in.n_ticks != 1 || !in.raw || (!CAN && !rpm) || state_nt(s.n * sb) ||
       c.pitch * 4 * 3 * kAxF >= 0xFFFFFFFFull)
     return (int)hipErrorNotSupported;
   KfArgs<MdEKF9, Ekf9Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, prm};
   a.prm.thlo = s.thlo;
   a.prm.clo = s.xlo;
   const bool nt = state_nt(ctrl_state_bytes(c) + s.n * sb);
-  const bool diag = ekf9_r_diagonal(prm.r);
-  if (s.xlo) return diag ? isr_ekf9_c<true, true, CAN>(a, c, p, frames, rpm, nt, libm, st, can)
-                         : isr_ekf9_c<false, true, CAN>(a, c, p, frames, rpm, nt, libm, st, can);
-  return diag ? isr_ekf9_c<true, false, CAN>(a, c, p, frames, rpm, nt, libm, st, can)
-              : isr_ekf9_c<false, false, CAN>(a, c, p, frames, rpm, nt, libm, st, can);
+  const unsigned lds = nt ? FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u) : 0u;
+  // CNT (CAN only): the EKF9 state and the motor state together past the Infinity Cache: the
+  // motor state streams non-temporal and the EKF9 state stays resident
+  with_bools([&](auto LIBM, auto SEQ, auto COMP, auto NT, auto CNT) {
+    if constexpr (CAN || !CNT())
+      k_isr_ekf9<LIBM(), SEQ(), NT() ? kStateNT : 0, COMP(), CAN, CNT()>
+          <<<grid_for(c.n), kBlock, lds, st>>>(a, c, p, frames, rpm, can);
+  }, libm, ekf9_r_diagonal(prm.r), s.xlo != nullptr, nt, CAN && can_nt_flag(can));
+  return (int)hipGetLastError();
 }
 
 // fmskf_isr_tick for EKF9 in one kernel where it applies: one tick, the tiled EKF9 state
@@ -808,55 +722,39 @@ int launch_kf12d(const DevState &s, const TickIn &in, const Kf12dParams &p, bool
                  hipStream_t st, int *ens_nb) {
   KfArgs<MdKF12D, Kf12dParams> a{s.n, s.pitch, (double *)s.x, (double *)s.P, in, s.counters, p};
   const dim3 g = grid_for(s.n);
-  const bool small = FMSKF_TILED || s.pitch * 8 * 78 < 0xFFFFFFFFull;  // tiled: any N
-  const bool nt = FMSKF_TILED && state_nt(s.n * 90 * 8);
-  const bool sp = p.sparse != 0;
+  const bool nt = state_nt(s.n * 90 * 8);
+  // SP (the default R and Q: sparse C^-1 and Q, checked on the host) implies BLK
+  const bool sp = p.sparse != 0, blk = kf12d_sequential(p.r);
   if (in.fold_blocks && !in.ens_blocks) return (int)hipErrorInvalidValue;
   if (in.ens_blocks) {
-    // fused tick + record (fmskf_tick_ensemble): the default kernel (decorrelated update,
-    // tiled state) with the record epilogue; one record per tick block
-    if (!FMSKF_TILED || !p.decor || !ens_nb || !upd || !pred || in.n_ticks != 1) return (int)hipErrorInvalidValue;
-    const bool blk = kf12d_sequential(p.r);
+    // fused tick + record (fmskf_tick_ensemble): the default kernel (decorrelated update) with
+    // the record epilogue; one record per tick block
+    if (!p.decor || !ens_nb || !upd || !pred || in.n_ticks != 1) return (int)hipErrorInvalidValue;
     a.in.ens_grid = g.x;
     const dim3 ge(g.x + (in.fold_blocks ? (unsigned)EnsRec<12>::LEN : 0u));  // + the carried fold
-    const hipEvent_t ev = in.ens_done;
-    if (sp && nt) launch_signal(k_kf12s<true, true, true, true, kStateNT, true, true>, ge, 0, st, ev, a);
-    else if (sp) launch_signal(k_kf12s<true, true, true, true, 0, true, true>, ge, 0, st, ev, a);
-    else if (blk && nt) launch_signal(k_kf12s<true, true, true, true, kStateNT, true>, ge, 0, st, ev, a);
-    else if (blk) launch_signal(k_kf12s<true, true, true, true, 0, true>, ge, 0, st, ev, a);
-    else if (nt) launch_signal(k_kf12s<false, true, true, true, kStateNT, true>, ge, 0, st, ev, a);
-    else launch_signal(k_kf12s<false, true, true, true, 0, true>, ge, 0, st, ev, a);
+    with_bools([&](auto BLK, auto SP, auto NT) {
+      if constexpr (BLK() || !SP())
+        launch_signal(k_kf12s<BLK(), true, true, NT() ? kStateNT : 0, true, SP()>, ge, 0, st, in.ens_done, a);
+    }, sp || blk, sp, nt);
     *ens_nb = (int)g.x;
     return (int)hipGetLastError();
   }
   if (p.decor) {
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF12D_LDS", nt, 0u);
-    // SP (the default R and Q: sparse C^-1 and Q, checked on the host) implies BLK; tiled
-    // state, so SMALL holds for any N
-    if (sp && small && upd && pred) {
-      if (nt) k_kf12s<true, true, true, true, kStateNT, false, true><<<g, kBlock, lds, st>>>(a);
-      else k_kf12s<true, true, true, true, 0, false, true><<<g, kBlock, lds, st>>>(a);
-      return (int)hipGetLastError();
+    if (upd && pred) {
+      const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF12D_LDS", nt, 0u);
+      with_bools([&](auto BLK, auto SP, auto NT) {
+        if constexpr (BLK() || !SP())
+          k_kf12s<BLK(), true, true, NT() ? kStateNT : 0, false, SP()><<<g, kBlock, lds, st>>>(a);
+      }, sp || blk, sp, nt);
+    } else if (upd) {
+      with_bools([&](auto BLK) { k_kf12s<BLK(), true, false><<<g, kBlock, 0, st>>>(a); }, blk);
+    } else {  // a predict runs no update: one (BLK = false) instantiation serves both
+      k_kf12s<false, false, true><<<g, kBlock, 0, st>>>(a);
     }
-    const bool blk = kf12d_sequential(p.r);
-#define KF12S(B, S)                                                          \
-  if (upd && pred && nt) k_kf12s<B, true, true, S, kStateNT><<<g, kBlock, lds, st>>>(a); \
-  else if (upd && pred) k_kf12s<B, true, true, S><<<g, kBlock, lds, st>>>(a); \
-  else if (upd) k_kf12s<B, true, false, S><<<g, kBlock, 0, st>>>(a);        \
-  else k_kf12s<B, false, true, S><<<g, kBlock, 0, st>>>(a);
-    if (blk && small) { KF12S(true, true) }
-    else if (blk) { KF12S(true, false) }
-    else if (small) { KF12S(false, true) }
-    else { KF12S(false, false) }
-#undef KF12S
-  } else if (kf12d_sequential(p.r)) {
-    if (upd && pred) k_kf12d<true, true, true><<<g, kBlock, 0, st>>>(a);
-    else if (upd) k_kf12d<true, true, false><<<g, kBlock, 0, st>>>(a);
-    else k_kf12d<true, false, true><<<g, kBlock, 0, st>>>(a);
-  } else {
-    if (upd && pred) k_kf12d<false, true, true><<<g, kBlock, 0, st>>>(a);
-    else if (upd) k_kf12d<false, true, false><<<g, kBlock, 0, st>>>(a);
-    else k_kf12d<false, false, true><<<g, kBlock, 0, st>>>(a);
+  } else if (upd) {
+    with_bools([&](auto SEQ, auto PRED) { k_kf12d<SEQ(), true, PRED()><<<g, kBlock, 0, st>>>(a); }, blk, pred);
+  } else {  // as above: one (SEQ = false) instantiation
+    k_kf12d<false, false, true><<<g, kBlock, 0, st>>>(a);
   }
   return (int)hipGetLastError();
 }

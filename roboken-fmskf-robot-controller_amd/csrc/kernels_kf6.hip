@@ -12,10 +12,10 @@
 //  * the 2 KiB TABLE512 sine table is staged in LDS (per wave in the single-tick kernel, per
 //    block in the loop kernels), so the trig lookups in the middle of the math wait on
 //    lgkmcnt only, never behind the state loads;
-//  * planes are addressed through buffer descriptors built from kernel arguments (T8) with
-//    a 32-bit lane byte offset; when the 21 P planes fit one 4 GiB window (n < 51M, the
-//    SMALL instantiation) one descriptor per array plus a per-plane scalar soffset
-//    addresses every plane, so the loop needs almost no scalar or vector address math;
+//  * the tiled state is addressed through buffer descriptors built from kernel arguments (T8):
+//    one descriptor per array over the lane's tile, a 32-bit lane byte offset and a per-row
+//    scalar soffset, so the loop needs almost no scalar or vector address math (the inputs:
+//    kf6_load_in, whose SMALL instantiation keeps the array-base form while n < 51M);
 //  * whether a validity mask exists is a compile-time choice (no conditional load whose
 //    merge would force a full vmcnt(0) drain);
 //  * tick_many loads the inputs of tick t+1 before computing tick t.
@@ -317,54 +317,24 @@ static void launch_sel(const KfArgs<MdKF6, Kf6Params> &a, hipStream_t st, int *e
   launch_o<O>(a, st);
 }
 
-template <bool LIBM, bool UPD, bool PRED, bool REC>
-static void launch_lupr_plain(const KfArgs<MdKF6, Kf6Params> &a, bool small, bool valid, hipStream_t st,
-                              int *nb) {
-  if (small) {
-    if (valid) launch_sel<Opt<LIBM, UPD, PRED, true, true, REC>>(a, st, nb);
-    else launch_sel<Opt<LIBM, UPD, PRED, true, false, REC>>(a, st, nb);
-  } else {
-    if (valid) launch_sel<Opt<LIBM, UPD, PRED, false, true, REC>>(a, st, nb);
-    else launch_sel<Opt<LIBM, UPD, PRED, false, false, REC>>(a, st, nb);
-  }
-}
-template <bool LIBM, bool UPD, bool PRED, bool REC>
-static void launch_lupr(const KfArgs<MdKF6, Kf6Params> &a, bool small, bool valid, hipStream_t st,
-                        int *nb) {
-  if (a.prm.lo) {  // FMSKF_CFG_COMP_POS
-    if (small) {
-      if (valid) launch_sel<Opt<LIBM, UPD, PRED, true, true, REC, false, false, true>>(a, st, nb);
-      else launch_sel<Opt<LIBM, UPD, PRED, true, false, REC, false, false, true>>(a, st, nb);
-    } else {
-      if (valid) launch_sel<Opt<LIBM, UPD, PRED, false, true, REC, false, false, true>>(a, st, nb);
-      else launch_sel<Opt<LIBM, UPD, PRED, false, false, REC, false, false, true>>(a, st, nb);
-    }
-    return;
-  }
-  launch_lupr_plain<LIBM, UPD, PRED, REC>(a, small, valid, st, nb);
-}
-template <bool LIBM, bool UPD, bool PRED>
-static void launch_lup(const KfArgs<MdKF6, Kf6Params> &a, bool small, bool valid, hipStream_t st,
-                       int *nb) {
-  if (UPD && a.in.rec) launch_lupr<LIBM, UPD, PRED, UPD>(a, small, valid, st, nb);
-  else launch_lupr<LIBM, UPD, PRED, false>(a, small, valid, st, nb);
-}
-
 int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, bool upd,
                bool pred, hipStream_t st, int *ens_nb) {
   KfArgs<MdKF6, Kf6Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p};
+  // Opt::SMALL (kf6_load_in's array-base input descriptors); the bound is a regime boundary
+  // inherited from the planar layout, whose 21 P planes had to fit one 4 GiB window
   const bool small = s.pitch * 84 < 0xFFFFFFFFull;
-  const bool valid = upd && in.valid != nullptr;
+  const bool valid = upd && in.valid != nullptr, rec = upd && in.rec != nullptr;
+  const bool comp = p.lo != nullptr;  // FMSKF_CFG_COMP_POS
   int *nb = in.ens_blocks && upd && pred && in.n_ticks == 1 ? ens_nb : nullptr;
   if ((in.ens_blocks && !nb) || (in.fold_blocks && !in.ens_blocks)) return (int)hipErrorInvalidValue;
-  if (libm) {
-    if (upd && pred) launch_lup<true, true, true>(a, small, valid, st, nb);
-    else if (upd) launch_lup<true, true, false>(a, small, valid, st, nullptr);
-    else launch_lup<true, false, true>(a, small, false, st, nullptr);
-  } else {
-    if (upd && pred) launch_lup<false, true, true>(a, small, valid, st, nb);
-    else if (upd) launch_lup<false, true, false>(a, small, valid, st, nullptr);
-    else launch_lup<false, false, true>(a, small, false, st, nullptr);
+  if (upd) {
+    with_bools([&](auto LIBM, auto PRED, auto REC, auto COMP, auto SMALL, auto VALID) {
+      launch_sel<Opt<LIBM(), true, PRED(), SMALL(), VALID(), REC(), false, false, COMP()>>(a, st, nb);
+    }, libm, pred, rec, comp, small, valid);
+  } else {  // a predict reads no input: SMALL, VALID and REC cannot change its code
+    with_bools([&](auto LIBM, auto COMP) {
+      launch_o<Opt<LIBM(), false, true, true, false, false, false, false, COMP()>>(a, st);
+    }, libm, comp);
   }
   return (int)hipGetLastError();
 }
@@ -373,25 +343,14 @@ int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool lib
 // Input descriptors are always the chunk-based form that is valid for any N (kf6_load_in without
 // SMALL).  No fused ensemble record and no compensated positions: the callers take the
 // stand-alone record / refuse the gate.
-template <bool LIBM, bool PRED>
-static void launch_gate_lp(const GateArgs &ga, hipStream_t st) {
-  const bool valid = ga.k.in.valid != nullptr;
-  if (ga.k.in.rec) {
-    if (valid) launch_o<Opt<LIBM, true, PRED, false, true, true>>(ga, st);
-    else launch_o<Opt<LIBM, true, PRED, false, false, true>>(ga, st);
-  } else {
-    if (valid) launch_o<Opt<LIBM, true, PRED, false, true, false>>(ga, st);
-    else launch_o<Opt<LIBM, true, PRED, false, false, false>>(ga, st);
-  }
-}
-
 int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,
                     bool pred, hipStream_t st) {
   if (p.lo || in.ens_blocks || in.fold_blocks || !g.word || !g.nis) return (int)hipErrorInvalidValue;
   if (!pred && in.n_ticks != 1) return (int)hipErrorInvalidValue;
   const GateArgs ga{{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p}, g};
-  if (libm) pred ? launch_gate_lp<true, true>(ga, st) : launch_gate_lp<true, false>(ga, st);
-  else pred ? launch_gate_lp<false, true>(ga, st) : launch_gate_lp<false, false>(ga, st);
+  with_bools([&](auto LIBM, auto PRED, auto VALID, auto REC) {
+    launch_o<Opt<LIBM(), true, PRED(), false, VALID(), REC()>>(ga, st);
+  }, libm, pred, in.valid != nullptr, in.rec != nullptr);
   return (int)hipGetLastError();
 }
 

@@ -65,7 +65,7 @@ int ensemble_nblocks(uint64_t n) {
 }
 
 // Partial: every block accumulates the shifted moment sums of its grid-stride robots and
-// writes its block record.  TILED (the EKF9 / KF12D state layout) is a compile-time choice:
+// writes its block record.  TILED (every state but the planar RS one) is a compile-time choice:
 // st_at then divides by the constant tile width (shifts), not by a runtime value.
 template <int NX, typename T, bool TILED, int R>
 __global__ __launch_bounds__(kBlock) void k_ens_partial(const T *__restrict__ x, uint64_t n,
@@ -125,29 +125,23 @@ static void ens_launch(const DevState &s, double *blocks, const double *shift, d
                        hipStream_t st) {
   const int nb = ensemble_nblocks(s.n);
   const int r = ens_r<NX>() < ens_rpl(s.n) ? ens_r<NX>() : ens_rpl(s.n);
-  auto go = [&](auto tiled, auto rr) {
-    k_ens_partial<NX, T, decltype(tiled)::value, decltype(rr)::value>
-        <<<nb, kBlock, 0, st>>>((const T *)s.x, s.n, s.pitch, shift, blocks);
+  auto go = [&](auto rr) {
+    with_bools([&](auto TILED) {
+      // the planar form exists for the RS record alone (NX = 6; launch_ensemble refuses the others)
+      if constexpr (TILED() || NX == 6)
+        k_ens_partial<NX, T, TILED(), decltype(rr)::value>
+            <<<nb, kBlock, 0, st>>>((const T *)s.x, s.n, s.pitch, shift, blocks);
+    }, s.tile != 0);
   };
-  using TT = std::true_type;
-  using TF = std::false_type;
-  using R2 = std::integral_constant<int, 2>;
-  using R4 = std::integral_constant<int, 4>;
-  using R8 = std::integral_constant<int, 8>;
-  if (s.tile) {
-    if (r == 2) go(TT{}, R2{});
-    else if (r == 8) go(TT{}, R8{});
-    else go(TT{}, R4{});
-  } else {
-    if (r == 2) go(TF{}, R2{});
-    else if (r == 8) go(TF{}, R8{});
-    else go(TF{}, R4{});
-  }
+  if (r == 2) go(std::integral_constant<int, 2>{});
+  else if (r == 8) go(std::integral_constant<int, 8>{});
+  else go(std::integral_constant<int, 4>{});
   if (out) fold_launch<NX>(blocks, nb, shift, out, st);
 }
 
 int launch_ensemble(const DevState &s, int nx, bool f64, double *blocks, const double *shift,
                     double *out, hipStream_t st) {
+  if (!s.tile && nx != 6) return (int)hipErrorInvalidValue;  // only the RS state is planar
   if (nx == 6 && !f64) ens_launch<6, float>(s, blocks, shift, out, st);
   else if (nx == 9 && !f64) ens_launch<9, float>(s, blocks, shift, out, st);
   else if (nx == 12 && f64) ens_launch<12, double>(s, blocks, shift, out, st);
@@ -181,11 +175,6 @@ int launch_ens_shift(const DevState &s, int nx, bool f64, double *shift, hipStre
 }  // namespace fmskf
 
 namespace fmskf {
-
-__global__ __launch_bounds__(kBlock) void k_fill64(uint64_t *p, uint64_t bits, uint64_t count) {
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i < count) p[i] = bits;
-}
 
 // tiled rows x N arrays (fmskf_internal.hpp st_at): one thread per element of the tiled span
 struct RowBits {
@@ -288,13 +277,6 @@ int launch_motor_sums(const uint32_t *lo, const int32_t *hi, int64_t *dst, uint6
   if (n == 0) return 0;
   if (to_prev) k_motor_sums<true><<<grid_stride(n), kBlock, 0, st>>>(lo, hi, dst, n, pitch);
   else k_motor_sums<false><<<grid_stride(n), kBlock, 0, st>>>(lo, hi, dst, n, pitch);
-  return (int)hipGetLastError();
-}
-
-int launch_fill64(void *p, uint64_t bits, uint64_t count, hipStream_t st) {
-  if (count == 0) return 0;
-  const dim3 g((unsigned)((count + kBlock - 1) / kBlock));
-  k_fill64<<<g, kBlock, 0, st>>>((uint64_t *)p, bits, count);
   return (int)hipGetLastError();
 }
 

@@ -181,7 +181,7 @@ static void launch_flag(const SelArgs &a, hipStream_t st) {
 
 // KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9 with the tiled state
 static bool list_model(const DevState &s) {
-  if (!FMSKF_TILED || !FMSKF_KF6_TILED || s.tile != tile_w<float>()) return false;
+  if (s.tile != tile_w<float>()) return false;
   const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
   return (ekf || s.model == FMSKF_MODEL_KF6) && !(ekf && (comp || !s.thlo));
 }

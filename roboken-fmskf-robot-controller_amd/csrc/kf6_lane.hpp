@@ -116,34 +116,23 @@ __device__ __forceinline__ Kf6In kf6_load_in(const TickIn &in, uint64_t n, uint6
   return m;
 }
 
+// The tiled state (fmskf_internal.hpp st_at, 2048 robots per tile row): the tile is wave-uniform
+// (a wave's 64 robots, the clamped ones included, lie in one 256-robot chunk), so each array is
+// one scalar descriptor over its tile and each row a scalar offset.  The pitch is not part of a
+// tiled address; load and store still take it (unnamed), because without the callers' dead read
+// of it four k_kf6p instantiations (libm, mask, records, fused record) get another register
+// allocation (81 -> 89 VGPRs): left for a change that is allowed to alter the compiled code
 template <class O>
-__device__ __forceinline__ void kf6_load_state(const float *xg, const float *Pg, uint64_t pp,
-                                               uint32_t i, float (&x)[6], float (&P)[21]) {
-  if constexpr (FMSKF_KF6_TILED) {
-    // tiled state (fmskf_internal.hpp st_at, 2048 robots per tile row): the tile is
-    // wave-uniform (a wave's 64 robots, the clamped ones included, lie in one 256-robot chunk),
-    // so each array is one scalar descriptor over its tile and each row a scalar offset
-    constexpr uint32_t W = tile_w<float>();
-    const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
-    const uint32_t c = (i - tl * W) * 4u;
-    const auto rx = rsrc(xg + (uint64_t)tl * (6 * W), 6 * W * 4), rp = rsrc(Pg + (uint64_t)tl * (21 * W), 21 * W * 4);
+__device__ __forceinline__ void kf6_load_state(const float *xg, const float *Pg, uint64_t, uint32_t i,
+                                               float (&x)[6], float (&P)[21]) {
+  constexpr uint32_t W = tile_w<float>();
+  const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
+  const uint32_t c = (i - tl * W) * 4u;
+  const auto rx = rsrc(xg + (uint64_t)tl * (6 * W), 6 * W * 4), rp = rsrc(Pg + (uint64_t)tl * (21 * W), 21 * W * 4);
 #pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = ld_f32<O::CP>(rx, c, k * W * 4);
+  for (int k = 0; k < 6; k++) x[k] = ld_f32<O::CP>(rx, c, k * W * 4);
 #pragma unroll
-    for (int k = 0; k < 21; k++) P[k] = ld_f32<O::CP>(rp, c, k * W * 4);
-  } else if constexpr (O::SMALL) {
-    const auto rx = rsrc(xg, pp * 24), rp = rsrc(Pg, pp * 84);
-    const uint32_t ps = (uint32_t)pp * 4u;
-#pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = ld_f32<O::CP>(rx, i * 4u, k * ps);
-#pragma unroll
-    for (int k = 0; k < 21; k++) P[k] = ld_f32<O::CP>(rp, i * 4u, k * ps);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 6; k++) x[k] = ld_f32<O::CP>(rsrc(xg + k * pp, pp * 4), i * 4u, 0);
-#pragma unroll
-    for (int k = 0; k < 21; k++) P[k] = ld_f32<O::CP>(rsrc(Pg + k * pp, pp * 4), i * 4u, 0);
-  }
+  for (int k = 0; k < 21; k++) P[k] = ld_f32<O::CP>(rp, c, k * W * 4);
 }
 
 // Write-back only where changed.  KF6 has constant F and H and rotates the wheel velocity by the
@@ -186,31 +175,17 @@ __device__ __forceinline__ void kf6_st_p(__amdgpu_buffer_rsrc_t r, uint32_t voff
 }
 
 template <class O>
-__device__ __forceinline__ void kf6_store_state(float *xg, float *Pg, uint64_t pp, uint32_t i,
-                                                const float (&x)[6], const float (&P)[21], const Kf6Old &old) {
+__device__ __forceinline__ void kf6_store_state(float *xg, float *Pg, uint64_t, uint32_t i, const float (&x)[6],
+                                                const float (&P)[21], const Kf6Old &old) {
   constexpr int SP = st_pol(O::CP);
-  if constexpr (FMSKF_KF6_TILED) {
-    constexpr uint32_t W = tile_w<float>();
-    const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
-    const uint32_t c = (i - tl * W) * 4u;
-    const auto rx = rsrc(xg + (uint64_t)tl * (6 * W), 6 * W * 4), rp = rsrc(Pg + (uint64_t)tl * (21 * W), 21 * W * 4);
+  constexpr uint32_t W = tile_w<float>();
+  const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
+  const uint32_t c = (i - tl * W) * 4u;
+  const auto rx = rsrc(xg + (uint64_t)tl * (6 * W), 6 * W * 4), rp = rsrc(Pg + (uint64_t)tl * (21 * W), 21 * W * 4);
 #pragma unroll
-    for (int k = 0; k < 6; k++) st_f32<SP>(rx, c, k * W * 4, x[k]);
+  for (int k = 0; k < 6; k++) st_f32<SP>(rx, c, k * W * 4, x[k]);
 #pragma unroll
-    for (int k = 0; k < 21; k++) kf6_st_p<SP>(rp, c, k * W * 4, k, P[k], old);
-  } else if constexpr (O::SMALL) {
-    const auto rx = rsrc(xg, pp * 24), rp = rsrc(Pg, pp * 84);
-    const uint32_t ps = (uint32_t)pp * 4u;
-#pragma unroll
-    for (int k = 0; k < 6; k++) st_f32<SP>(rx, i * 4u, k * ps, x[k]);
-#pragma unroll
-    for (int k = 0; k < 21; k++) kf6_st_p<SP>(rp, i * 4u, k * ps, k, P[k], old);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 6; k++) st_f32<SP>(rsrc(xg + k * pp, pp * 4), i * 4u, 0, x[k]);
-#pragma unroll
-    for (int k = 0; k < 21; k++) kf6_st_p<SP>(rsrc(Pg + k * pp, pp * 4), i * 4u, 0, k, P[k], old);
-  }
+  for (int k = 0; k < 21; k++) kf6_st_p<SP>(rp, c, k * W * 4, k, P[k], old);
 }
 
 // the COMP low-part rows, tiled like x ([N/W][5][W], one scalar descriptor per tile)

@@ -1,7 +1,9 @@
-"""GPU parity at sizes past the 4 GiB buffer window: the kernels' SMALL instantiations
-address every plane array through one buffer descriptor with 32-bit offsets; beyond 4 GiB of
-planes they switch to 64-bit addressing.  These runs take the large path and check a sample
-of robots (first, last and random ones) against the oracle bit for bit."""
+"""GPU parity at sizes where a whole state array passes the 4 GiB window of one buffer
+descriptor.  The tiled arrays are addressed per tile and need no such window, but the launchers
+still change regime there: the KF6 tick takes kf6_load_in's chunk-based input descriptors
+(Opt::SMALL off), the control step gives up its non-temporal instantiation and the fused ISR
+gives way to three kernels.  These runs take the large path and check a sample of robots
+(first, last and random ones) against the oracle bit for bit."""
 import numpy as np
 import pytest
 
@@ -20,7 +22,7 @@ def _sample(n, k=2048, seed=0):
 def test_kf6_past_the_buffer_window(orc):
     import torch
     from fmskf.synth import kf6_ring_torch
-    n, T = 52_000_000, 3          # pitch * 84 B > 4 GiB -> 64-bit plane addressing
+    n, T = 52_000_000, 3          # pitch * 84 B > 4 GiB -> the launcher drops Opt::SMALL
     assert fmskf_pitch(n) * 84 > 0xFFFFFFFF
     yaw, gz, rpm = kf6_ring_torch(n, T, seed=99, device="cuda")
     with Engine("kf6", n) as e:
@@ -77,7 +79,7 @@ def test_kf6_headline_instantiation_2p20(orc):
 @pytest.mark.parametrize("n", [36_000_000, 46_000_000])
 def test_control_past_the_buffer_window(orc, n):
     """36M: the 36 interpolator planes (144 B per robot) pass 4 GiB while the 24 FF_PI_D planes
-    do not (the SMALL choice must follow the larger array); 46M: both pass."""
+    do not (the launcher's window test follows the larger array); 46M: both pass."""
     import torch
     T = 40
     assert fmskf_pitch(n) * 4 * 36 > 0xFFFFFFFF

@@ -154,8 +154,7 @@ def rotate(e, o, inp, t):
 @pytest.mark.parametrize("model", MODELS)
 def test_create_and_reset_write_every_p0_entry(orc, model, case, n):
     """after fmskf_create, and again after some ticks and fmskf_reset: x = 0 and every entry of P,
-    off-diagonals included, is the narrowed p0 (do_reset: the tiled fill of EKF9 / KF12D, the
-    per-plane fills of KF6)"""
+    off-diagonals included, is the narrowed p0 (do_reset: the tiled fill of every row)"""
     prm = pc.case(model, case)
     nx, _, dtype = pc.DIMS[model]
     want = np.repeat(np.asarray(prm.p0, dtype)[:, None], n, 1)
@@ -202,6 +201,39 @@ def run_case(orc, model, case, n, seed=40):
 @pytest.mark.parametrize("model,case", ALL)
 def test_case_bitexact(orc, model, case, n):
     run_case(orc, model, case, n)
+
+
+# ----------------------------------------------------------------------------- correct / predict alone
+@pytest.mark.parametrize("model,case,form,n", [("kf6", "default", "planes", 2321), ("kf6", "default", "rec", 2321),
+                                               ("kf12d", "default", "planes", 4369),
+                                               ("kf12d", "r_dense", "planes", 4369)])
+def test_correct_and_predict_alone_beside_masked_ticks(orc, model, case, form, n):
+    """fmskf_correct with a `valid` mask and fmskf_predict, each checked on its own, between masked
+    full ticks of the same handle: KF6 fed planes and fed records, KF12D with the default R (SP) and
+    with a non-sequential R (!BLK).  A predict reads no input, so the launchers give it one
+    instantiation whatever the mask, the input form and R are.  N: one full tile (2048 fp32 / 4096
+    fp64 robots), one more 256-robot chunk and a 17-robot tail, an odd chunk count (the
+    two-per-lane KF6 kernel gets a chunk without a partner)."""
+    prm = pc.default_params(model) if case == "default" else pc.case(model, case)
+    if model == "kf12d":
+        assert pc.kf12d_path(orc, prm) == ("SP" if case == "default" else pc.PATHS[case])
+    T = 6
+    inp = Inputs(model, n, T, 52)
+    o = Oracle(orc, prm, n)
+    with Engine(model, n, **pc.engine_kw(prm)) as e:
+        for t in range(T):
+            v, what = inp.valid[t], f"{model} {case} {form} n={n} t={t}"
+            if t % 2 == 0:
+                e.tick(valid=v, **inp.kw(t, form))
+                o.tick(inp, t, v)
+            else:
+                e.correct(valid=v, **inp.kw(t, form))
+                o.tick(inp, t, v, pred=False)
+                o.same(e, what + ": correct alone")
+                e.predict()
+                o.tick(inp, t, None, upd=False)
+            o.same(e, what)
+        assert e.get_counters()[0] == 0
 
 
 # ----------------------------------------------------------------------------- fused record

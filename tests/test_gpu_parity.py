@@ -881,7 +881,7 @@ def test_tick_ensemble_fused_ekf9_libm_mask(orc, n):
                                      ("kf12d", 3 * 256), ("rs", 300)])
 def test_state_round_trip_and_reset(model, n):
     """fmskf_set_state / get_state round-trip the dense planes bit for bit whatever the device
-    layout (tiled for EKF9 / KF12D, planar pitch for KF6 / RS), from host and from device
+    layout (tiled for KF6 / EKF9 / KF12D, planar pitch for RS), from host and from device
     memory, at ragged N; fmskf_reset restores x = 0 and P = P0 in every row."""
     import torch
     rng = np.random.default_rng(n)
