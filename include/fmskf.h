@@ -400,6 +400,99 @@ int fmskf_correct_pose(fmskf_handle h, const fmskf_pose_fix *fixes, uint64_t cou
                        float *nis, uint8_t *status,   /* [count], either may be NULL */
                        uint32_t mem);
 
+/* ---- range updates against surveyed anchors (KF6, EKF9) ------------------------- */
+/* A UWB tag does not deliver a position: it delivers one range to one anchor at a time, in short
+ * bursts of two to four anchors.  fmskf_correct_range fuses each range directly into the listed
+ * robot's current estimate -- one scalar measurement with its own gate, linearised on that
+ * estimate; the antenna's lever arm makes the heading observable -- instead of a multilaterated
+ * position with an invented covariance through fmskf_correct_pose.
+ *
+ * Anchors.  The handle owns a device table of up to FMSKF_RANGE_ANCHORS_MAX surveyed anchors, one
+ * 16-byte row (x, y, z, 0) each.  fmskf_set_anchors replaces the table from host xyz [count][3]
+ * (the copy is ordered on the handle's stream); count == 0 clears it.  FMSKF_EINVAL for count >
+ * FMSKF_RANGE_ANCHORS_MAX, a NULL xyz with count > 0, a non-finite coordinate, and inside a graph
+ * capture.  fmskf_get_anchors writes min(count, capacity) rows to host xyz (NULL with capacity 0:
+ * the count alone) and the table's size to *count.  Anchors are configuration: fmskf_reset keeps
+ * them, and checkpoints neither write nor read them (the file of a handle with anchors is byte
+ * for byte that of one without).
+ *
+ * The measurement, in fp32, every operation rounded on its own (no contraction), with correctly
+ * rounded square root and divisions, in this order.  (c, s) = the handle's own cos / sin of the
+ * heading state (fmskf_config.trig, as fmskf_eval_trig evaluates it; EKF9: of the heading's high
+ * part); (lx, ly, lz) = prm->tag; (ax, ay, az) the anchor; r the entry's var_m2 when > 0, else
+ * prm->var_m2:
+ *     rx = c*lx - s*ly            ry = s*lx + c*ly
+ *     dx = (px - ax) + rx         dy = (py - ay) + ry         dz = lz - az
+ *          with FMSKF_CFG_COMP_POS  dx = ((px_hi - ax) + px_lo) + rx, dy likewise
+ *     d  = sqrt((dx*dx + dy*dy) + dz*dz)
+ *     !(d >= d_min):  status FMSKF_RANGE_NEAR, d2 = 0, nothing is touched (a NaN d included)
+ *     di = 1/d        H = (dx*di, dy*di, (dy*rx - dx*ry)*di, 0, ...)
+ *     hp[j] = (H0*P[0][j] + H1*P[1][j]) + H2*P[2][j]           j = 0 .. n-1 (the high parts of P)
+ *     S  = ((H0*hp[0] + H1*hp[1]) + H2*hp[2]) + r
+ *     si = 1/S        y = range_m - d        g = y*si        d2 = y*g
+ *     apply = d2 <= d2_max                   (+INFINITY: no gate; a NaN d2 never applies)
+ *     applied:  x[j] = x[j] + hp[j]*g        P[i][j] = P[i][j] - (hp[i]*si)*hp[j]   (i >= j)
+ * The EKF9 heading takes its term by TwoSum into its low part and is renormalised; with
+ * FMSKF_CFG_COMP_POS px, py, P00, P10 and P11 take theirs by TwoSum into the low-part rows and are
+ * renormalised.  Both renormalisations follow every applied entry, so that a burst in one call
+ * equals the same entries in successive calls bit for bit.  No predict runs and the heading is
+ * not wrapped again (as in fmskf_correct_pose).  The handle's persistent gates are neither read
+ * nor changed, and the call keeps nothing between calls.
+ *
+ * Lists.  `robot` is non-descending.  A run -- a maximal sequence of consecutive entries with the
+ * same robot, one burst -- is applied in list order, each entry on the state the one before
+ * left, by one pass over the robot's rows: they are read once and written once, and only if an
+ * entry was applied.  status[k]: FMSKF_GATE_ACCEPTED, FMSKF_GATE_REJECTED, FMSKF_RANGE_NEAR or
+ * FMSKF_FIX_IGNORED; d2[k]: the evaluated d2, 0 for a NEAR or ignored entry.  Either may be NULL;
+ * every entry's outputs are written exactly once.  An entry is ignored when
+ *   - its run's first entry has robot >= N (the whole run),
+ *   - its run's first entry has a robot below its predecessor's (the whole run),
+ *   - its own anchor is at or above the table's size (that entry alone is skipped), or
+ *   - the entry FMSKF_RANGE_RUN_MAX places before it has the same robot (a run's entries past
+ *     the first FMSKF_RANGE_RUN_MAX).
+ * A host list is validated before anything is launched: any of these is FMSKF_EINVAL and nothing
+ * changes.  A device list (16-byte aligned) cannot be validated on the host: the kernel ignores
+ * such entries and counts them in fmskf_get_counters slot [5].  A device list that is unsorted in
+ * some other way (5, 3, 5) is a caller error: no access leaves the handle's arrays, but the
+ * result for robots whose entries are not consecutive is unspecified.
+ *
+ * FMSKF_ENOTSUP for RS, KF12D and EKF9 with FMSKF_CFG_COMP_POS (the models fmskf_correct_pose
+ * refuses).  FMSKF_EINVAL for: no anchors set; a NULL prm; var_m2 not finite or <= 0; d2_max NaN
+ * or <= 0; d_min not finite or <= 0; a non-finite tag; flags or reserved not 0; a bad mem; a NULL
+ * list with count > 0; a host list inside a graph capture; count > FMSKF_RANGE_RUN_MAX * N.
+ * count == 0 is FMSKF_OK with no launch.  Host lists and outputs are staged like
+ * fmskf_correct_pose's (complete on return); with device pointers the call is asynchronous on the
+ * handle's stream and can be captured by fmskf_graph_begin.  fmskf_set_timing records the launch;
+ * a robot that an applied entry leaves non-finite is counted in counter [0] (a robot whose every
+ * entry is rejected, NEAR or ignored is neither stored nor counted). */
+#define FMSKF_RANGE_ANCHORS_MAX 1024u
+#define FMSKF_RANGE_RUN_MAX 8u     /* entries of one robot in one call */
+#define FMSKF_RANGE_NEAR 5         /* status: predicted distance below d_min, nothing done */
+
+int fmskf_set_anchors(fmskf_handle h, const float *xyz /* host [count][3] */, uint32_t count);
+int fmskf_get_anchors(fmskf_handle h, float *xyz, uint32_t capacity, uint32_t *count);
+
+typedef struct fmskf_range_fix {   /* 16 bytes, one per measured range */
+  uint32_t robot;
+  uint32_t anchor;                 /* index into the anchor table */
+  float range_m;
+  float var_m2;                    /* > 0: this range's variance; anything else: prm->var_m2 */
+} fmskf_range_fix;
+
+typedef struct fmskf_range_params {
+  float tag[3];    /* antenna: lx, ly in the body frame [m], lz its height in the anchors' z frame */
+  float var_m2;    /* default range variance, finite, > 0 */
+  float d2_max;    /* apply when d2 <= d2_max; > 0; +INFINITY: no gate; NaN d2 never applies */
+  float d_min;     /* finite, > 0: below it the direction is undefined -> FMSKF_RANGE_NEAR */
+  uint32_t flags;  /* must be 0 */
+  uint32_t reserved; /* must be 0 */
+} fmskf_range_params;
+
+int fmskf_correct_range(fmskf_handle h, const fmskf_range_fix *fixes, uint64_t count,
+                        const fmskf_range_params *prm,
+                        float *d2, uint8_t *status,   /* [count], either may be NULL */
+                        uint32_t mem);
+
 /* ---- robots selected by their state; state of listed robots (KF6, EKF9) --------- */
 /* The per-robot signals of the entry points above -- a state gone non-finite (counter [0] says
  * that some did, not which), a position covariance grown too large, a gate that keeps rejecting
@@ -562,7 +655,14 @@ int fmskf_get_motor_status(fmskf_handle h, int16_t *microsec_id, int16_t *angle,
  * [2] count since create / reset and are not checkpointed.  [3] = entries of device fix lists
  * that fmskf_correct_pose ignored as malformed (FMSKF_FIX_IGNORED); since create / reset, not
  * checkpointed either.  [4] = entries of device robot lists that fmskf_get_state_subset /
- * fmskf_set_state_subset ignored as malformed; since create / reset, not checkpointed. */
+ * fmskf_set_state_subset ignored as malformed; since create / reset, not checkpointed.
+ * [5] = entries of device range lists that fmskf_correct_range ignored (FMSKF_FIX_IGNORED: a run
+ * whose first entry has robot >= N or a robot below its predecessor's, an anchor index at or
+ * above the table's size, a run's entries past the first FMSKF_RANGE_RUN_MAX); since create /
+ * reset, not checkpointed.  fmskf_correct_range counts in [0] the robots it stores non-finite, as
+ * fmskf_correct_pose does: a robot with a NaN in P00, P10 or P11 has a NaN d2, is
+ * FMSKF_GATE_REJECTED and is not counted; one with a NaN px or py has a NaN predicted distance,
+ * is FMSKF_RANGE_NEAR and is not counted either. */
 int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters);
 
 /* ---- ensemble statistics (mean / covariance of x across instances) --------- */

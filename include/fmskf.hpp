@@ -112,6 +112,22 @@ class Robots {
     check(fmskf_correct_pose(h_, fixes, count, &prm, nis, status, mem), "fmskf_correct_pose");
   }
 
+  // the handle's table of surveyed anchors (fmskf_set_anchors: host xyz [count][3], count 0 clears
+  // it; reset and checkpoints leave it alone) and single ranges to them fused into the listed
+  // robots (fmskf_correct_range: a UWB callback; `robot` non-descending, the consecutive entries
+  // of one robot -- a burst -- applied in order): d2 / status [count] receive the evaluated d2 and
+  // FMSKF_GATE_ACCEPTED / _REJECTED / FMSKF_RANGE_NEAR / FMSKF_FIX_IGNORED, either may be NULL
+  void set_anchors(const float *xyz, uint32_t count) { check(fmskf_set_anchors(h_, xyz, count), "fmskf_set_anchors"); }
+  uint32_t get_anchors(float *xyz, uint32_t capacity) {
+    uint32_t count = 0;
+    check(fmskf_get_anchors(h_, xyz, capacity, &count), "fmskf_get_anchors");
+    return count;
+  }
+  void correct_range(const fmskf_range_fix *fixes, uint64_t count, const fmskf_range_params &prm,
+                     float *d2 = nullptr, uint8_t *status = nullptr, uint32_t mem = FMSKF_MEM_HOST) {
+    check(fmskf_correct_range(h_, fixes, count, &prm, d2, status, mem), "fmskf_correct_range");
+  }
+
   // the robots for which any criterion of prm holds (fmskf_select: a state gone non-finite, a
   // position covariance above a threshold, a gate that keeps rejecting), strictly ascending --
   // the list correct_pose and the subset calls take.  robots / reason [capacity] (reason may be

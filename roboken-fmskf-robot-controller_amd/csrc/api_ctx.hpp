@@ -8,6 +8,7 @@
 //   api_ctrl.cpp        control step, CAN TX, the fused ISR, VehicleInfo, timing
 //   api_fix.cpp         fmskf_correct_pose
 //   api_select.cpp      fmskf_select, fmskf_get_state_subset / fmskf_set_state_subset
+//   api_range.cpp       fmskf_set_anchors / fmskf_get_anchors, fmskf_correct_range
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -184,6 +185,15 @@ struct fmskf_ctx {
   // fmskf_get_state_subset / fmskf_set_state_subset: malformed entries of device robot lists
   // (fmskf_get_counters [4]), a word of its own for the same reason
   unsigned long long *subset_ignored = nullptr;
+  // fmskf_correct_range: the anchor table (FMSKF_RANGE_ANCHORS_MAX rows of 16 bytes: x, y, z, 0;
+  // allocated with the handle, so nothing is allocated under a capture), the host's copy of the
+  // rows in use (what fmskf_set_anchors queued and fmskf_get_anchors returns), and the ignored
+  // entries of device range lists (fmskf_get_counters [5]).  Configuration: reset keeps the table,
+  // no checkpoint holds it.
+  float *anchors = nullptr;
+  std::vector<float> anchors_host;  // [n_anchors][4]
+  uint32_t n_anchors = 0;
+  unsigned long long *range_ignored = nullptr;
   // fmskf_select scratch, allocated on its first call (fmskf_internal.hpp SelectDev): the reason
   // byte of every robot, the count of every 256-robot block, the scan of the chunk sums.  Not
   // state: every call rewrites what it reads, and no checkpoint holds it.

@@ -231,6 +231,7 @@ void do_reset(fmskf_ctx *h) {
   hip_check(hipMemsetAsync(s.counters, 0, 8 * 8, st), "reset counters");
   hip_check(hipMemsetAsync(h->fix_ignored, 0, 8, st), "reset counters");
   hip_check(hipMemsetAsync(h->subset_ignored, 0, 8, st), "reset counters");
+  hip_check(hipMemsetAsync(h->range_ignored, 0, 8, st), "reset counters");  // the anchors stay
   h->isr_can_split = h->isr_ctrl_split = 0;
   h->rs_prev_synced = h->rs_prev_stale = false;  // the prev planes were zeroed above
   h->ctrl_derived_stale = false;                  // and the control outputs
@@ -507,6 +508,8 @@ int fmskf_create(const fmskf_config *cfg, fmskf_handle *out) {
       s.counters = h->alloc<unsigned long long>(8);
       h->fix_ignored = h->alloc<unsigned long long>(1);
       h->subset_ignored = h->alloc<unsigned long long>(1);
+      h->range_ignored = h->alloc<unsigned long long>(1);
+      h->anchors = h->alloc<float>((size_t)FMSKF_RANGE_ANCHORS_MAX * 4);
       s.sintab = h->alloc<float>(513);
       {
         // the fused KF6 tick + record (fmskf_tick_ensemble) writes one record per tick block

@@ -168,11 +168,15 @@ int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters) 
     unsigned long long sub_ignored = 0;  // the subset get / set: malformed device-list entries
     hip_check(hipMemcpyAsync(&sub_ignored, h->subset_ignored, sizeof(sub_ignored), hipMemcpyDeviceToHost, h->stream),
               "D2H");
+    unsigned long long rng_ignored = 0;  // fmskf_correct_range: ignored device-list entries
+    hip_check(hipMemcpyAsync(&rng_ignored, h->range_ignored, sizeof(rng_ignored), hipMemcpyDeviceToHost, h->stream),
+              "D2H");
     hip_check(hipStreamSynchronize(h->stream), "sync");
     tmp[1] = h->isr_can_split;  // host-side counters: the launch forms the ISR calls took
     tmp[2] = h->isr_ctrl_split;
     tmp[3] = ignored;
     tmp[4] = sub_ignored;
+    tmp[5] = rng_ignored;
     for (uint32_t k = 0; k < n_counters && k < 8; k++) counters[k] = tmp[k];
   });
 }

@@ -200,6 +200,21 @@ struct PoseFixDev {
   float nis_max;
   uint32_t m;       // 2: z = (px, py); 3: z = (px, py, theta)
 };
+// One fmskf_correct_range call as its kernel sees it (kernels_range.hip; an argument struct of its
+// own): the non-descending list of 16-byte fmskf_range_fix entries, the handle's anchor table
+// (16-byte rows x, y, z, 0), the optional per-entry outputs (device pointers) and the call's
+// parameters
+struct RangeDev {
+  const uint32_t *fixes;  // [count] x 16 B fmskf_range_fix: robot, anchor, range_m, var_m2
+  uint64_t count;
+  const float *anchors;   // [n_anchors] x 16 B
+  uint32_t n_anchors;
+  float *d2;        // [count] or null
+  uint8_t *status;  // [count] or null
+  unsigned long long *ignored;  // the handle's count of ignored entries (fmskf_get_counters [5])
+  float tag[3];
+  float var, d2_max, d_min;
+};
 // One fmskf_select call as its kernels see it (kernels_select.hip; argument structs of their own,
 // nothing is added to the tick kernels').  Scratch of the handle: flag [N] the reason byte of
 // every robot (0: not selected), blk [ceil(N / 256)] the selected robots of every 256-robot block,
@@ -452,6 +467,9 @@ int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_
 // the absolute pose-fix update of the listed robots (kernels_fix.hip): KF6 (plain and
 // FMSKF_CFG_COMP_POS) and EKF9 (plain); hipErrorNotSupported otherwise
 int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st);
+// the range updates of the listed robots against the anchor table (kernels_range.hip): the models
+// of launch_pose_fix; libm: the handle's sin / cos policy
+int launch_range_fix(const DevState &s, const RangeDev &f, bool libm, hipStream_t st);
 // fmskf_select (kernels_select.hip): the flag pass over the robots, the scan of the block counts
 // (two launches), the ordered emit; the models of launch_pose_fix
 int launch_select(const DevState &s, const SelectDev &d, hipStream_t st);

@@ -1,6 +1,6 @@
 // list_rows.hpp -- the tiled state rows of one robot addressed per lane, for the kernels that
-// work on a list of robots (kernels_fix.hip: fmskf_correct_pose; kernels_select.hip: the subset
-// get / set).
+// work on a list of robots (kernels_fix.hip: fmskf_correct_pose; kernels_range.hip:
+// fmskf_correct_range; kernels_select.hip: the subset get / set).
 //
 // The state is tiled [ceil(N / 2048)][rows][2048] (fmskf_internal.hpp st_at) and a wave's listed
 // robots lie in arbitrary tiles, so the wave-uniform per-chunk descriptors of the tick kernels do

@@ -33,6 +33,10 @@ GATE_NONE, GATE_ACCEPTED, GATE_REJECTED, GATE_FORCED = range(4)
 # fmskf_correct_pose: FMSKF_FIX_HEADING (flag), FMSKF_FIX_IGNORED (status of a malformed entry)
 FIX_HEADING = 1
 FIX_IGNORED = 4
+# fmskf_correct_range: FMSKF_RANGE_ANCHORS_MAX, FMSKF_RANGE_RUN_MAX, FMSKF_RANGE_NEAR (status)
+RANGE_ANCHORS_MAX = 1024
+RANGE_RUN_MAX = 8
+RANGE_NEAR = 5
 
 MODEL_NAMES = {"rs": MODEL_RS, "kf6": MODEL_KF6, "ekf9": MODEL_EKF9, "kf12d": MODEL_KF12D}
 
@@ -97,6 +101,15 @@ class PoseFixParams(C.Structure):
     _fields_ = [("r", C.c_double * 6), ("nis_max", C.c_float), ("flags", C.c_uint32)]
 
 
+class RangeFix(C.Structure):
+    _fields_ = [("robot", C.c_uint32), ("anchor", C.c_uint32), ("range_m", C.c_float), ("var_m2", C.c_float)]
+
+
+class RangeParams(C.Structure):
+    _fields_ = [("tag", C.c_float * 3), ("var_m2", C.c_float), ("d2_max", C.c_float), ("d_min", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # fmskf_select criteria (FMSKF_SEL_*), also the bits of its reason bytes
 SEL_NONFINITE, SEL_POS_VAR, SEL_GATE_RUN = 1, 2, 4
 
@@ -159,6 +172,9 @@ SIGNATURES = {
     "fmskf_set_row_gate": (C.c_int, [_H, C.POINTER(RowGate)]),
     "fmskf_get_row_gate": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_correct_pose": (C.c_int, [_H, _P, C.c_uint64, C.POINTER(PoseFixParams), _P, _P, C.c_uint32]),
+    "fmskf_set_anchors": (C.c_int, [_H, _P, C.c_uint32]),
+    "fmskf_get_anchors": (C.c_int, [_H, _P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "fmskf_correct_range": (C.c_int, [_H, _P, C.c_uint64, C.POINTER(RangeParams), _P, _P, C.c_uint32]),
     "fmskf_select": (C.c_int, [_H, C.POINTER(SelectParams), _P, _P, C.c_uint64, _P, C.c_uint32]),
     "fmskf_get_state_subset": (C.c_int, [_H, _P, C.c_uint64, _P, _P, _P, C.c_uint32]),
     "fmskf_set_state_subset": (C.c_int, [_H, _P, C.c_uint64, _P, _P, _P, C.c_uint32]),

@@ -14,8 +14,8 @@ import numpy as np
 from . import _lib
 from ._lib import (MEM_DEVICE, MEM_HOST, MODEL_EKF9, MODEL_KF6, MODEL_KF12D, MODEL_NAMES,
                    MODEL_RS, TRIG_LIBM, TRIG_TABLE512, Config, CtrlParams, ENOTSUP, FIX_HEADING, FmskfError,
-                   EKF9_ROWS, Gate, PoseFixParams, ROW_GATE_D2, RowGate, SEL_GATE_RUN, SEL_NONFINITE, SEL_POS_VAR,
-                   SelectParams, TickInputs, check, load)
+                   EKF9_ROWS, Gate, PoseFixParams, RANGE_ANCHORS_MAX, RangeParams, ROW_GATE_D2, RowGate, SEL_GATE_RUN,
+                   SEL_NONFINITE, SEL_POS_VAR, SelectParams, TickInputs, check, load)
 
 # fmskf_vehicle_info (include/fmskf.h): the VehicleInfo message layout, 84 bytes
 VEHICLE_INFO_DTYPE = np.dtype([("pos_x", "<i4"), ("pos_y", "<i4"), ("pos_theta", "<f4"),
@@ -29,6 +29,9 @@ KF6_RECORD_DTYPE = np.dtype([("yaw_deg", "<f4"), ("gyro_z_dps", "<f4"), ("rpm", 
 
 # fmskf_pose_fix (include/fmskf.h): one absolute pose fix, 16 bytes
 POSE_FIX_DTYPE = np.dtype([("robot", "<u4"), ("x_m", "<f4"), ("y_m", "<f4"), ("theta_rad", "<f4")])
+
+# fmskf_range_fix (include/fmskf.h): one measured range to one anchor, 16 bytes
+RANGE_FIX_DTYPE = np.dtype([("robot", "<u4"), ("anchor", "<u4"), ("range_m", "<f4"), ("var_m2", "<f4")])
 
 _DTYPES = {
     "yaw_deg": np.float32, "gyro_z_dps": np.float32, "rpm": np.int16, "angle_sum": np.int64,
@@ -76,6 +79,29 @@ def pose_fix_records(robot, x, y, theta=None):
     rec["y_m"] = y
     if theta is not None:
         rec["theta_rad"] = theta
+    return rec
+
+
+def range_fix_records(robot, anchor, range_m, var=None):
+    """Pack measured ranges ([count] robot indices, non-descending; anchor indices into the
+    handle's table; ranges in metres; var: each range's variance in m^2 or None for the call's
+    default; all numpy or all torch device tensors) into fmskf_range_fix's: numpy -> [count]
+    RANGE_FIX_DTYPE, torch -> [count, 4] int32."""
+    if _is_torch(robot):
+        import torch
+        rec = torch.zeros((robot.shape[0], 4), dtype=torch.int32, device=robot.device)
+        rec[:, 0] = robot.to(torch.int32)  # the low 32 bits
+        rec[:, 1] = anchor.to(torch.int32)
+        for k, v in ((2, range_m), (3, var)):
+            if v is not None:
+                rec[:, k] = v.to(torch.float32).contiguous().view(torch.int32)
+        return rec
+    rec = np.zeros(np.shape(robot), RANGE_FIX_DTYPE)
+    rec["robot"] = robot
+    rec["anchor"] = anchor
+    rec["range_m"] = range_m
+    if var is not None:
+        rec["var_m2"] = var
     return rec
 
 
@@ -327,6 +353,70 @@ class Engine:
         ps = a.ptr(status) if status is not None else None
         check(load().fmskf_correct_pose(self.h, pf, count, C.byref(prm), pn, ps, mem), "correct_pose")
         return (nis, status) if nis is not None or status is not None else None
+
+    # ------------------------------------------------------------------ ranges against anchors
+    def set_anchors(self, xyz):
+        """fmskf_set_anchors: replace the handle's anchor table with xyz [count, 3] (metres; a
+        host array); an empty array clears it."""
+        a = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        check(load().fmskf_set_anchors(self.h, a.ctypes.data_as(C.c_void_p), a.shape[0]), "set_anchors")
+
+    def get_anchors(self):
+        """fmskf_get_anchors: the anchor table, [count, 3] float32"""
+        out = np.zeros((RANGE_ANCHORS_MAX, 3), np.float32)
+        cnt = C.c_uint32()
+        check(load().fmskf_get_anchors(self.h, out.ctypes.data_as(C.c_void_p), RANGE_ANCHORS_MAX, C.byref(cnt)),
+              "get_anchors")
+        return out[:cnt.value].copy()
+
+    def correct_range(self, robot=None, anchor=None, range_m=None, var=None, *, fixes=None, tag=(0.0, 0.0, 0.0),
+                      var_default, d2_max=float("inf"), d_min, out=False):
+        """fmskf_correct_range: fuse measured ranges to the anchors of set_anchors() into the
+        listed robots (KF6, EKF9).  `robot` [count] non-descending (the consecutive entries of one
+        robot, a burst, are applied in order) with anchor, range_m and optionally var (per-range
+        variances; entries <= 0 take var_default), numpy arrays or torch device tensors; or `fixes`,
+        records packed by range_fix_records().  tag: the antenna (lx, ly in the body frame, lz its
+        height); d2_max: apply a range only when its normalised innovation squared <= d2_max;
+        d_min: below this predicted distance nothing is done (RANGE_NEAR).  out=True returns (d2
+        [count] float32, status [count] uint8: GATE_ACCEPTED / GATE_REJECTED / RANGE_NEAR /
+        FIX_IGNORED) as numpy arrays (host list) or torch tensors (device list); out=(d2, status)
+        writes into the given device tensors (a call that is captured)."""
+        if fixes is None:
+            fixes = range_fix_records(robot, anchor, range_m, var)
+        prm = RangeParams()
+        for k in range(3):
+            prm.tag[k] = float(tag[k])
+        prm.var_m2 = float(var_default)
+        prm.d2_max = float(d2_max)
+        prm.d_min = float(d_min)
+        a = _Args()
+        if _is_torch(fixes):
+            if str(fixes.dtype) != "torch.int32" or fixes.dim() != 2 or fixes.shape[1] != 4:
+                raise TypeError("fixes: want a [count, 4] int32 tensor (range_fix_records)")
+            count = int(fixes.shape[0])
+            pf = a.ptr(fixes)
+        else:
+            fixes = np.ascontiguousarray(fixes)
+            if fixes.dtype != RANGE_FIX_DTYPE:
+                raise TypeError("fixes: want RANGE_FIX_DTYPE records (range_fix_records)")
+            count = int(fixes.size)
+            pf = a.ptr(fixes.view(np.uint32))
+        mem = MEM_HOST if a.mem is None else a.mem
+        d2 = status = None
+        if isinstance(out, tuple):
+            d2, status = out
+            if mem != MEM_DEVICE:
+                raise TypeError("out tensors go with a device range list")
+        elif out and mem == MEM_DEVICE:
+            import torch
+            d2 = torch.zeros(count, dtype=torch.float32, device=fixes.device)
+            status = torch.zeros(count, dtype=torch.uint8, device=fixes.device)
+        elif out:
+            d2, status = np.zeros(count, np.float32), np.zeros(count, np.uint8)
+        pd = a.ptr(d2) if d2 is not None else None
+        ps = a.ptr(status) if status is not None else None
+        check(load().fmskf_correct_range(self.h, pf, count, C.byref(prm), pd, ps, mem), "correct_range")
+        return (d2, status) if d2 is not None or status is not None else None
 
     # ------------------------------------------------------------------ selection, listed robots
     def select(self, nonfinite=False, pos_var_min=None, gate_run_min=None, row_mask=None, capacity=None,
@@ -968,5 +1058,5 @@ def default_config(model="kf6", n=1) -> Config:
     return cfg
 
 
-__all__ = ["Engine", "pose_fix_records", "POSE_FIX_DTYPE", "ensemble_combine", "default_config", "comm_unique_id", "VEHICLE_INFO_DTYPE", "MODEL_RS", "MODEL_KF6", "MODEL_EKF9",
+__all__ = ["Engine", "pose_fix_records", "POSE_FIX_DTYPE", "range_fix_records", "RANGE_FIX_DTYPE", "ensemble_combine", "default_config", "comm_unique_id", "VEHICLE_INFO_DTYPE", "MODEL_RS", "MODEL_KF6", "MODEL_EKF9",
            "MODEL_KF12D", "TRIG_TABLE512", "TRIG_LIBM", "_lib"]

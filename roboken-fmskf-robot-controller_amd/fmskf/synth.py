@@ -279,6 +279,38 @@ def pose_fixes(traj, t, every: int = 32, start: int = 8, sigma: float = 1e-2, ou
     return robot.astype(np.uint32), x.astype(np.float32), y.astype(np.float32), th.astype(np.float32), outlier
 
 
+def range_fixes(traj, t, anchors, tag=(0.0, 0.0, 0.0), every: int = 32, start: int = 8, run: int = 3,
+                sigma: float = 0.05, outlier_share: float = 0.05, outlier_start: int = 40, seed: int = SEED):
+    """UWB ranges (fmskf_correct_range) for the call made before tick `t` of `traj`: the robots with
+    (i + t) % every == 0 for t >= start (none before), each with a burst of `run` consecutive
+    entries to the anchors (t // every + k + i) % len(anchors), k = 0 .. run - 1.  anchors
+    [A, 3] metres; tag (lx, ly in the body frame, lz the antenna's height).  The truth is that of
+    pose_fixes: traj.px[t - 1], traj.py[t - 1], traj.th[t]; a range is the distance from the
+    antenna to the anchor with Gaussian noise `sigma` (m).  From tick `outlier_start` on an
+    independent `outlier_share` of the ranges is lengthened by 0.5 - 2 m (a non-line-of-sight path
+    only lengthens).  Returns (robot [count] uint32 non-descending, anchor [count] uint32, range_m
+    [count] f32, outlier [count] bool)."""
+    anchors = np.asarray(anchors, np.float64).reshape(-1, 3)
+    if t < start or t < 1 or run < 1:
+        return np.zeros(0, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.float32), np.zeros(0, bool)
+    i = np.repeat(np.arange((-t) % every, traj.n, every, dtype=np.int64), run)
+    k = np.tile(np.arange(run, dtype=np.int64), i.size // run)
+    anchor = (t // every + k + i) % anchors.shape[0]
+    rng = np.random.default_rng([seed, 0x72616E67, t])
+    c = i.size
+    th = traj.th[t, i]
+    cs, sn = np.cos(th), np.sin(th)
+    dx = traj.px[t - 1, i] + cs * tag[0] - sn * tag[1] - anchors[anchor, 0]
+    dy = traj.py[t - 1, i] + sn * tag[0] + cs * tag[1] - anchors[anchor, 1]
+    dz = tag[2] - anchors[anchor, 2]
+    rho = np.sqrt(dx * dx + dy * dy + dz * dz) + rng.normal(0.0, sigma, c)
+    u = rng.random(c)
+    extra = rng.uniform(0.5, 2.0, c)
+    outlier = (u < outlier_share) & (t >= outlier_start)
+    rho = np.where(outlier, rho + extra, rho)
+    return i.astype(np.uint32), anchor.astype(np.uint32), rho.astype(np.float32), outlier
+
+
 def kf6_ring_torch(n: int, ticks: int, seed: int = SEED, device="cuda"):
     """Bench input ring generated directly in HBM (same sensor model as Trajectory,
     vectorised in torch float64 on the GPU; generation is not timed).

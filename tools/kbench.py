@@ -53,6 +53,11 @@ def main():
                     help="KF6 / EKF9: time the absolute pose-fix pass (fmskf_correct_pose) alone, by kernel time as "
                          "--ktime does, with this share of the robots listed (1: every robot, 0.03125: one in 32)")
     ap.add_argument("--fix-m", type=int, choices=[2, 3], default=3, help="--pose-fix: 3 = with the heading")
+    ap.add_argument("--range-fix", type=float, default=None, metavar="DENSITY",
+                    help="KF6 / EKF9: time the range pass (fmskf_correct_range, four anchors) alone, by kernel time "
+                         "as --pose-fix does, with this share of the robots listed")
+    ap.add_argument("--range-run", type=int, default=1, metavar="K",
+                    help="--range-fix: K consecutive ranges (a burst) per listed robot, 1 to 8")
     ap.add_argument("--select", choices=["all", "pos_var", "nonfinite", "subset"], default=None,
                     help="KF6 / EKF9: time fmskf_select (a POS_VAR-only select with 0.1 %%, 3 %% and 100 %% of the robots "
                          "selected; a NONFINITE select with 0.1 %% planted) and the subset get / set of listed robots "
@@ -151,6 +156,8 @@ def main():
         preps = [e.prepare(valid=vm[r], **kws[r]) for r in range(R)]
     if args.pose_fix is not None:
         return bench_pose_fix(args, e, n, preps, dev)
+    if args.range_fix is not None:
+        return bench_range_fix(args, e, n, preps, dev)
     if args.select is not None:
         return bench_select(args, e, n, preps, dev, st)
     if args.host:
@@ -363,6 +370,66 @@ def bench_pose_fix(args, e, n, preps, dev):
                       "line_bytes_per_fix_est": rows * 128 * 2 * lines_per_fix_row + 16,
                       "line_MB_per_pass_est": robot.size * (rows * 128 * 2 * lines_per_fix_row + 16) / 1e6,
                       "ignored": e.get_counters()[3],
+                      "finite": bool(np.isfinite(x).all() and np.isfinite(P).all())}), flush=True)
+
+
+def bench_range_fix(args, e, n, preps, dev):
+    """The range pass alone at a given density (robots 0, s, 2 s, ... with s = round(1 / density),
+    each with a burst of --range-run ranges to four anchors at about (+-6, +-6, 2.5) m), kernel time
+    per launch as bench_pose_fix takes it: back to back, and each pass right behind a tick, with
+    the tick's own kernel time from the same run."""
+    import numpy as np
+    import torch
+    import fmskf
+    R = len(preps)
+    for k in range(20):
+        e.tick_prepared(preps[k % R])
+    stride = max(1, int(round(1.0 / args.range_fix)))
+    run = min(max(args.range_run, 1), fmskf.RANGE_RUN_MAX)
+    anchors = np.array([[6.0, 6.1, 2.5], [-6.2, 5.9, 2.4], [-5.9, -6.0, 2.6], [6.1, -6.2, 2.5]], np.float32)
+    tag = (0.15, 0.05, 0.30)
+    e.set_anchors(anchors)
+    robots = np.arange(0, n, stride, dtype=np.int64)
+    robot = np.repeat(robots, run)
+    anchor = (robot + np.tile(np.arange(run), robots.size)) % 4
+    pose = e.get_pose()[:, robot].astype(np.float64)
+    c, s = np.cos(pose[2]), np.sin(pose[2])
+    dx = pose[0] + c * tag[0] - s * tag[1] - anchors[anchor, 0]
+    dy = pose[1] + s * tag[0] + c * tag[1] - anchors[anchor, 1]
+    rho = np.sqrt(dx * dx + dy * dy + (tag[2] - anchors[anchor, 2]) ** 2)
+    rho += np.random.default_rng(1).normal(0.0, 0.05, rho.size)
+    rec = fmskf.range_fix_records(robot.astype(np.uint32), anchor.astype(np.uint32), rho.astype(np.float32))
+    rec = torch.from_numpy(rec.view(np.int32).reshape(-1, 4)).to(dev)
+    kw = dict(fixes=rec, tag=tag, var_default=0.0025, d_min=0.5)
+    for _ in range(5):
+        e.correct_range(**kw)
+    e.set_timing(True)
+    for _ in range(args.ticks):
+        e.correct_range(**kw)
+    tot, cnt = e.kernel_time_total()
+    back_to_back = tot * 1e3 / max(cnt, 1)
+    tick_ms = fix_ms = 0.0
+    for k in range(args.ticks):
+        e.set_timing(True)
+        e.tick_prepared(preps[(20 + k) % R])
+        tick_ms += e.kernel_time_total()[0]
+        e.set_timing(True)
+        e.correct_range(**kw)
+        fix_ms += e.kernel_time_total()[0]
+    e.set_timing(False)
+    comp = 5 if args.comp else 0
+    rows = {"kf6": 27 + comp, "ekf9": 54 + 1}[args.model]
+    # line traffic per listed robot as bench_pose_fix counts it, plus 16 bytes per entry
+    lines_per_row = min(1.0, stride / 32.0)
+    x, P = e.get_state()
+    print(json.dumps({"model": args.model, "n": n, "op": "range_fix", "comp": args.comp, "run": run,
+                      "density": 1.0 / stride, "robots": int(robots.size), "count": int(robot.size),
+                      "range_kernel_us": back_to_back, "range_kernel_us_after_tick": fix_ms * 1e3 / args.ticks,
+                      "tick_kernel_us": tick_ms * 1e3 / args.ticks,
+                      "state_bytes_per_robot": rows * 4 * 2 + 16 * run,
+                      "line_bytes_per_robot_est": rows * 128 * 2 * lines_per_row + 16 * run,
+                      "line_MB_per_pass_est": robots.size * (rows * 128 * 2 * lines_per_row + 16 * run) / 1e6,
+                      "ignored": e.get_counters()[5],
                       "finite": bool(np.isfinite(x).all() and np.isfinite(P).all())}), flush=True)
 
 
