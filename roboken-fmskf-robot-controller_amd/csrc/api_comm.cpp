@@ -35,6 +35,34 @@ void ens_fold_queued(fmskf_ctx *h, fmskf_ctx::EnsSlot &S) {
   else hip_check(hipEventRecord(S.done, h->stream), "hipEventRecord");
   h->ens_carry = -1;
 }
+// A tick kernel carries the fold of the newest event (ens_fold_front): the slot goes into the
+// launch's inputs, and once the launch is queued the fold counts as queued.  Shared by the record
+// tick of the next event (ens_async_begin) and the plain KF6 tick behind an event (run_tick).
+fmskf_ctx::EnsSlot *ens_carry_attach(fmskf_ctx *h, TickIn &t) {
+  if (h->ens_carry < 0) return nullptr;
+  fmskf_ctx::EnsSlot &C = h->eslot[h->ens_carry];
+  t.fold_blocks = C.blocks;
+  t.fold_nb = (uint32_t)C.nb;
+  t.fold_out = ens_fold_dst(h, C);
+  t.ens_shift = h->ens_shift;
+  // one GPU, untimed: the carrying kernel's own completion records C's event
+  if (!ens_exchanges(h) && !h->timing) t.ens_done = C.done;
+  return &C;
+}
+void ens_carry_launched(fmskf_ctx *h, fmskf_ctx::EnsSlot *C, const TickIn &t) {
+  if (!C) return;
+  if (t.ens_done) h->ens_carry = -1;  // recorded by the kernel's completion signal
+  else ens_fold_queued(h, *C);
+}
+// FMSKF_ENS_CARRY_PLAIN=0 (read once): a plain tick carries no fold; the event's fold runs
+// stand-alone ahead of it, as ahead of every other call (the tests' and the A/B's reference)
+bool ens_carry_plain() {
+  static const bool on = [] {
+    const char *e = getenv("FMSKF_ENS_CARRY_PLAIN");
+    return !e || atoi(e) != 0;
+  }();
+  return on;
+}
 // the stand-alone fold of the newest event, when no tick kernel carried it
 void ens_flush(fmskf_ctx *h) {
   if (h->ens_carry < 0) return;
@@ -324,8 +352,9 @@ namespace {
 // PREVIOUS event's records (ens_fold_front) | the stand-alone partial.  The previous event's fold is
 // then queued: its `done` event (one GPU: the fold wrote the pinned host slot itself) or, with
 // a communicator, the all-gather and D2H on the side stream.  This event's own fold waits for
-// the next event's tick kernel, or runs stand-alone ahead of a plain tick, at
-// fmskf_ensemble_end or before a shift rewrite (ens_flush).
+// the next event's tick kernel or the next plain KF6 tick (run_tick), whichever comes first, or
+// runs stand-alone: ahead of any other call, at fmskf_ensemble_end or before a shift rewrite
+// (ens_flush).
 // Nothing waits on the host.
 
 void ens_async_begin(fmskf_ctx *h, const fmskf_tick_inputs *in) {
@@ -363,14 +392,7 @@ void ens_async_begin(fmskf_ctx *h, const fmskf_tick_inputs *in) {
     TickIn t = resolve_inputs(h, in, true, true, 1, h->s.n);
     t.ens_blocks = S.blocks;
     t.ens_shift = h->ens_shift;
-    fmskf_ctx::EnsSlot *C = h->ens_carry >= 0 ? &h->eslot[h->ens_carry] : nullptr;
-    if (C) {
-      t.fold_blocks = C->blocks;
-      t.fold_nb = (uint32_t)C->nb;
-      t.fold_out = ens_fold_dst(h, *C);
-      // one GPU, untimed: the carrying kernel's own completion records C's event
-      if (!ens_exchanges(h) && !h->timing) t.ens_done = C->done;
-    }
+    fmskf_ctx::EnsSlot *C = ens_carry_attach(h, t);
     const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
     h->time_begin();
     int e = 0;
@@ -379,10 +401,7 @@ void ens_async_begin(fmskf_ctx *h, const fmskf_tick_inputs *in) {
     else e = launch_kf12d(h->s, t, h->kf12, true, true, h->stream, &nb);
     launch_check(e, "tick kernel launch");
     h->time_end();
-    if (C) {
-      if (t.ens_done) h->ens_carry = -1;  // recorded by the kernel's completion signal
-      else ens_fold_queued(h, *C);
-    }
+    ens_carry_launched(h, C, t);
   } else {
     ens_flush(h);
     if (in) run_tick(h, in, true, true, 1, h->s.n);

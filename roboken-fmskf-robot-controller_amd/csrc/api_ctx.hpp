@@ -137,9 +137,10 @@ struct fmskf_ctx {
   // kEnsSlots events in flight, each slot with its own block records, record, gather buffer and
   // pinned host copy.  A slot is reused only after fmskf_ensemble_end consumed it (its `done`
   // event, behind the fold, was waited for), so the tick that rewrites a slot's block records
-  // needs no stream wait.  Event k's fold rides in the next event's tick kernel (extra blocks
-  // ahead of its tick blocks: ens_fold_front), or runs stand-alone when a plain tick or a result
-  // request comes first (ens_flush); with a communicator the side stream `ens_stream`
+  // needs no stream wait.  Event k's fold rides in the next event's tick kernel or in the next
+  // direct plain KF6 tick (extra blocks ahead of its tick blocks: ens_fold_front), or runs
+  // stand-alone when any other call or a result request comes first (ens_flush); with a
+  // communicator the side stream `ens_stream`
   // all-gathers it while the tick stream runs on.
   static constexpr int kEnsSlots = 4;
   struct EnsSlot {
@@ -449,6 +450,9 @@ void copy_out_sync(fmskf_ctx *h, void *dst, const void *src, size_t bytes, uint3
 // api_comm.cpp
 double *ens_fold_dst(const fmskf_ctx *h, const fmskf_ctx::EnsSlot &S);
 void ens_fold_queued(fmskf_ctx *h, fmskf_ctx::EnsSlot &S);
+fmskf_ctx::EnsSlot *ens_carry_attach(fmskf_ctx *h, TickIn &t);
+void ens_carry_launched(fmskf_ctx *h, fmskf_ctx::EnsSlot *C, const TickIn &t);
+bool ens_carry_plain();
 void ens_flush(fmskf_ctx *h);
 void ensure_shift(fmskf_ctx *h);
 bool fused_record(const fmskf_ctx *h);

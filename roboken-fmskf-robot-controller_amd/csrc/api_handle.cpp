@@ -346,11 +346,18 @@ void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, ui
   check_handle(h);
   DeviceGuard g(h->cfg.device);
   TickIn t = resolve_inputs(h, in, upd, pred, n_ticks, stride);
-  // a plain tick after an asynchronous ensemble event: the event's fold runs stand-alone
-  // ahead of it (a record every K > 1 ticks gets its result one fold after its tick; only the
-  // next ensemble tick's kernel carries it).  Not inside a capture: the replay would fold
-  // whatever the slot holds then
-  if (!h->capturing) ens_flush(h);
+  // a plain call after an asynchronous ensemble event: a direct full single KF6 tick (ungated,
+  // so the plain kernels) carries the event's fold in the blocks ahead of its tick blocks, as the
+  // next event's record tick would (ens_carry_attach; a record every K > 1 ticks then costs no
+  // launch of its own between two ticks); ahead of every other call the fold runs stand-alone.
+  // Not inside a capture: the replay would fold whatever the slot holds then
+  fmskf_ctx::EnsSlot *C = nullptr;
+  if (!h->capturing) {
+    if (h->cfg.model == FMSKF_MODEL_KF6 && fused_record(h) && upd && pred && n_ticks == 1 && ens_carry_plain())
+      C = ens_carry_attach(h, t);
+    else
+      ens_flush(h);
+  }
   const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
   const bool rs_pred = h->cfg.model == FMSKF_MODEL_RS && pred;
   if (rs_pred) rs_prev_materialize(h);  // the predict reads the prev planes
@@ -363,6 +370,7 @@ void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, ui
     case FMSKF_MODEL_KF12D: e = launch_kf12d(h->s, t, h->kf12, upd, pred, h->stream); break;
   }
   launch_check(e, "tick kernel launch");
+  ens_carry_launched(h, C, t);
   // the predict stored the sums it read as the previous ones
   if (rs_pred) h->rs_prev_synced = t.msum_lo != nullptr;
   h->time_end();

@@ -123,9 +123,9 @@ struct TickIn {
   double *ens_blocks;
   const double *ens_shift;
   uint32_t ens_grid;  // the tick blocks (= block records); set by the launcher
-  // fmskf_tick_ensemble_begin: the previous event's block records ([LEN][fold_nb]), folded by
-  // LEN extra blocks at the front of this tick's grid into fold_out (ens_fold_front); null
-  // otherwise
+  // fmskf_tick_ensemble_begin, and the plain KF6 tick right behind one: the previous event's
+  // block records ([LEN][fold_nb]), folded by LEN extra blocks at the front of this tick's grid
+  // into fold_out (ens_fold_front); null otherwise
   uint32_t fold_nb;
   const double *fold_blocks;
   double *fold_out;

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void k_isr_kf6(KfArgs<MdKF6, Kf6Params> a, 
   float *stab = wtab[O::LIBM ? 0 : threadIdx.x >> 6];
   WaveTable<O::LIBM> tv(a.in.sintab);
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
-  const Kf6Old old = kf6_keep_old(P);
+  const Kf6Old<> old = kf6_keep_old(P);  // the narrow mask (kKf6SkipMask)
   Kf6In m = kf6_load_in<O>(a.in, n, 0, ic);
   CtrlLane<CPC> L;
   L.load(c, ic);

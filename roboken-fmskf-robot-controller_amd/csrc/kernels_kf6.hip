@@ -5,7 +5,16 @@
 // (yaw, gyro z, 4 wheel rpm -> z, the reference's deg2rad / mecanum FK / rotation,
 // VD_vehicle_controller.cpp:21-51) + LDL^T-form update + F P F^T + Q predict, one read and
 // one write of every state byte: 232 algorithmic bytes per instance-tick (the write of the
-// planes in kKf6SkipMask, kf6_lane.hpp, is issued only where a lane's value changed).
+// masked cross-covariance planes, kf6_lane.hpp, is issued only where a lane's value changed).
+// The mask belongs to the launch regime (kf6_wide below): the two-per-lane full tick takes all
+// eight cross planes (Opt WIDE) while state + inputs fill at most half the Infinity Cache, every
+// other launch their position half (kKf6SkipMask); the kernels without WIDE are the code they
+// were before the split (profiles/kf6_half_cache_bodies.json).
+//
+// A plain full tick launched right behind an asynchronous ensemble event carries that event's
+// fold (Opt FOLD): the LEN fold blocks of ens_fold_front ahead of its tick blocks, as the record
+// tick of the next event would carry them, and no record epilogue.  The host decides (run_tick);
+// a launch without a pending fold takes the plain instantiation, whose code FOLD does not touch.
 //
 // Memory-path design (MI355X_MICROARCH.md: s_waitcnt vmcnt is in-order, so any load issued
 // after the state loads makes every later wait cover them):
@@ -65,7 +74,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   Kf6GateOf<O, A> gt;
   Kf6In ma, mb;
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
-  const Kf6Old old = kf6_keep_old(P);  // as loaded: compared after the launch's last tick
+  const auto old = kf6_keep_old<kf6_mask<O>()>(P);  // as loaded: compared after the launch's last tick
   kf6_load_lo<O>(a.prm.lo, ic, lo);
   gt.load(gate_dev(aa), ic, n);
   if (O::UPD) ma = kf6_load_in<O>(a.in, n, 0, ic);
@@ -92,7 +101,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
 template <int WPE, class O>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6t(Kf6Args a) {
   uint32_t bid = blockIdx.x;
-  if constexpr (O::ENS) {
+  if constexpr (O::ENS || O::FOLD) {
     if (ens_fold_front<6>(a.in, bid)) return;
   }
   const uint64_t n = a.n;
@@ -109,7 +118,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   Kf6Lo<O> lo;
   Kf6Gate<O, false> gt;
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
-  const Kf6Old old = kf6_keep_old(P);
+  const auto old = kf6_keep_old<kf6_mask<O>()>(P);
   kf6_load_lo<O>(a.prm.lo, ic, lo);
   if (O::UPD) m = kf6_load_in<O>(a.in, n, 0, ic);
   tv.store(stab);
@@ -135,12 +144,12 @@ template <int WPE, int R, class O, class A = Kf6Args>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_kf6p(A aa) {
   const Kf6Args &a = kf_args(aa);
   uint32_t bid = blockIdx.x;
-  if constexpr (O::ENS) {
+  if constexpr (O::ENS || O::FOLD) {
     if (ens_fold_front<6>(a.in, bid)) return;
   }
   const uint64_t n = a.n;
   const uint32_t nn = (uint32_t)n, last = nn - 1u;
-  const uint32_t G = (O::ENS ? a.in.ens_grid : gridDim.x) * kBlock;
+  const uint32_t G = (O::ENS || O::FOLD ? a.in.ens_grid : gridDim.x) * kBlock;
   const uint32_t i0 = bid * kBlock + threadIdx.x;
   float x[6], P[21];
   __shared__ float wtab[O::LIBM ? 1 : kBlock / 64][O::LIBM ? 1 : kWaveTab];
@@ -160,7 +169,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
     Kf6Lo<O> lo;
     Kf6GateOf<O, A> gt;
     kf6_load_state<O>(a.x, a.P, a.pitch, live ? i : last, x, P);
-    const Kf6Old old = kf6_keep_old(P);
+    const auto old = kf6_keep_old<kf6_mask<O>()>(P);
     kf6_load_lo<O>(a.prm.lo, live ? i : last, lo);
     gt.load(gate_dev(aa), live ? i : last, n);
     if (r == 0) tv.store(stab);
@@ -230,6 +239,33 @@ static Kf6Regime kf6_regime(uint64_t n, uint64_t sb, bool rec, bool two_nt) {
   return {false, nt, FMSKF_LDS_CAP("FMSKF_KF6_LDS", nt, 48u * 1024u)};
 }
 
+// Which write-back mask a two-per-lane full tick (ungated, not COMP) takes: the eight cross planes
+// (Opt WIDE) while state + one tick's inputs fill at most half the Infinity Cache, the position
+// half past that.  The split is NOT the hardware's: the wide mask measured faster at 2^21 and 2^24
+// too (profiles/kf6_skip_store_ab.json).  It is the roofline check's: tests/test_gpu_bench_line.py
+// prices every KF6 row at the algorithmic 232 B per robot-tick and wants the row below that model's
+// bandwidth ceiling, and the project holds every KF6-fed row of a --full line to frac <= 0.97.
+// With the wide mask the 2^21 shard row read 0.983; the headline regime has room (0.913;
+// profiles/kf6_half_cache_ab.json).
+// FMSKF_KF6_SKIP_WIDE (read once): 0 narrow in every regime, 1 wide in every two-per-lane full
+// tick, unset by the regime.  sb: state bytes per robot
+static bool kf6_wide(uint64_t n, uint64_t sb) {
+  static const int force = [] {
+    const char *e = getenv("FMSKF_KF6_SKIP_WIDE");
+    return e ? atoi(e) : -1;
+  }();
+  if (force == 0 || force == 1) return force == 1;
+  return n * (sb + 16) <= (128ull << 20);
+}
+
+// A FOLD instantiation on the tick grid g: the LEN fold blocks of the pending ensemble event
+// ahead of the tick blocks, as launch_ens_o launches a record tick that carries one
+template <class A>
+static void launch_fold(void (*k)(A), A a, unsigned g, unsigned lds, hipStream_t st) {
+  a.in.ens_grid = g;
+  launch_signal(k, dim3(g + (unsigned)EnsRec<6>::LEN), lds, st, a.in.ens_done, a);
+}
+
 // One robot per lane: k_kf6t, or for a gated handle k_kf6p's single-robot form, the shape its
 // one-per-lane launches always had (the inputs are loaded ahead of the state; through k_kf6t the
 // gated tick at 2^24 measured 642-643 us against 633, profiles/gate_fold_ab.json)
@@ -237,6 +273,7 @@ template <class O, class A>
 static void launch_one(const A &aa, unsigned lds, hipStream_t st) {
   const dim3 g = grid_for(kf_args(aa).n);
   if constexpr (std::is_same<A, GateArgs>::value) k_kf6p<4, 1, O, A><<<g, kBlock, lds, st>>>(aa);
+  else if constexpr (O::FOLD) launch_fold(k_kf6t<4, O>, aa, g.x, lds, st);
   else k_kf6t<4, O><<<g, kBlock, lds, st>>>(aa);
 }
 
@@ -259,13 +296,28 @@ static void launch_o(const A &aa, hipStream_t st) {
     if (r.two) {
       const unsigned g = (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock));
       if constexpr (NT && !GATED) {
-        if (r.nt) {
-          k_kf6p<4, 2, WithNT<O>, A><<<g, kBlock, r.lds, st>>>(aa);
+        // the ungated full tick: streamed, with the wide mask (kf6_wide; never COMP, whose
+        // kernels stay as they were) and / or carrying a pending ensemble fold (run_tick)
+        const bool wide = !O::COMP && kf6_wide(a.n, 108), fold = a.in.fold_blocks != nullptr;
+        if (r.nt || wide || fold) {
+          with_bools([&](auto N, auto W, auto F) {
+            using ON = std::conditional_t<N(), WithNT<O>, O>;
+            using OW = std::conditional_t<W() && !O::COMP, WithWide<ON>, ON>;
+            if constexpr (F()) launch_fold(k_kf6p<4, 2, WithFold<OW>, A>, aa, g, r.lds, st);
+            else k_kf6p<4, 2, OW, A><<<g, kBlock, r.lds, st>>>(aa);
+          }, r.nt, wide, fold);
           return;
         }
       }
       k_kf6p<4, 2, O, A><<<g, kBlock, r.lds, st>>>(aa);
       return;
+    }
+    if constexpr (NT && !GATED) {
+      if (a.in.fold_blocks) {  // one robot per lane, carrying a pending ensemble fold
+        if (r.nt) launch_one<WithFold<WithNT<O>>>(aa, r.lds, st);
+        else launch_one<WithFold<O>>(aa, r.lds, st);
+        return;
+      }
     }
     if constexpr (NT) {
       if (r.nt) {
@@ -290,9 +342,17 @@ static int launch_ens_o(KfArgs<MdKF6, Kf6Params> a, hipStream_t st) {
   if (a.n * RB <= (256ull << 20)) {
     const unsigned g = (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock));
     a.in.ens_grid = g;
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF6P_LDS", true, 32u * 1024u);
-    if (state_nt(a.n * SB)) launch_signal(k_kf6p<4, 2, WithNT<E>>, dim3(g + carry), lds, st, a.in.ens_done, a);
-    else launch_signal(k_kf6p<4, 2, E>, dim3(g + carry), lds, st, a.in.ens_done, a);
+    // 32 KiB in every regime, not the plain record-fed tick's 48 KiB at 2^20 (kf6_regime): the
+    // record epilogue wants the fifth block per CU.  kbench ens_async, records, 2^20, three
+    // alternating passes on one box: K = 1 36.18-36.37 us per tick at 32 KiB against 38.08-38.20 at
+    // 48 KiB; the bench's K = 16 region shape (20 ticks, one event) 34.29-34.47 against 34.47-34.49
+    const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF6PE_LDS", true, 32u * 1024u);
+    // the write-back mask of the plain tick of the same regime (kf6_wide)
+    with_bools([&](auto N, auto W) {
+      using EN = std::conditional_t<N(), WithNT<E>, E>;
+      using EW = std::conditional_t<W() && !O::COMP, WithWide<EN>, EN>;
+      launch_signal(k_kf6p<4, 2, EW>, dim3(g + carry), lds, st, a.in.ens_done, a);
+    }, state_nt(a.n * SB), !O::COMP && kf6_wide(a.n, SB));
     return (int)g;
   }
   // past the Infinity Cache the record epilogue (fp64 sums and their cross-lane reduction)
@@ -326,7 +386,10 @@ int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool lib
   const bool valid = upd && in.valid != nullptr, rec = upd && in.rec != nullptr;
   const bool comp = p.lo != nullptr;  // FMSKF_CFG_COMP_POS
   int *nb = in.ens_blocks && upd && pred && in.n_ticks == 1 ? ens_nb : nullptr;
-  if ((in.ens_blocks && !nb) || (in.fold_blocks && !in.ens_blocks)) return (int)hipErrorInvalidValue;
+  // a carried fold rides on a full single tick alone: with the record epilogue (launch_ens_o) or,
+  // for a plain tick, in the FOLD instantiations (launch_o)
+  if ((in.ens_blocks && !nb) || (in.fold_blocks && !(upd && pred && in.n_ticks == 1)))
+    return (int)hipErrorInvalidValue;
   if (upd) {
     with_bools([&](auto LIBM, auto PRED, auto REC, auto COMP, auto SMALL, auto VALID) {
       launch_sel<Opt<LIBM(), true, PRED(), SMALL(), VALID(), REC(), false, false, COMP()>>(a, st, nb);

@@ -24,6 +24,8 @@ struct Opt {
   static constexpr bool LIBM = LIBM_, UPD = UPD_, PRED = PRED_, SMALL = SMALL_, VALID = VALID_,
                         REC = REC_, NT = NT_, ENS = ENS_, COMP = COMP_;
   static constexpr int CP = NT_ ? kStateNT : 0;
+  static constexpr bool WIDE = false, FOLD = false;
+  using Plain = Opt;
 };
 template <class O>
 using WithNT = Opt<O::LIBM, O::UPD, O::PRED, O::SMALL, O::VALID, O::REC, true, O::ENS, O::COMP>;
@@ -31,6 +33,21 @@ template <class O>
 using WithEns = Opt<O::LIBM, O::UPD, O::PRED, O::SMALL, O::VALID, O::REC, O::NT, true, O::COMP>;
 template <class O>
 using WithComp = Opt<O::LIBM, O::UPD, O::PRED, O::SMALL, O::VALID, O::REC, O::NT, O::ENS, true>;
+// WIDE: the write-back mask holds all eight cross-covariance planes (kKf6SkipWide below) instead
+// of their position half; chosen per launch regime (kernels_kf6.hip kf6_wide)
+// FOLD: a plain tick whose grid has the fold blocks of a pending ensemble event ahead of its tick
+// blocks (ens_device.hpp ens_fold_front), as the ENS kernels have, but writes no record itself
+// Both ride on a type derived from the Opt, not on two more parameters of it: a parameter, even
+// a defaulted one, is part of every instantiation's symbol, and the kernels without either trait
+// keep theirs.  WithNT / WithEns / WithComp build a plain Opt, so these two are applied last.
+template <class O, bool WIDE_, bool FOLD_>
+struct OptX : O {
+  static constexpr bool WIDE = WIDE_, FOLD = FOLD_;
+};
+template <class O>
+using WithWide = OptX<typename O::Plain, true, O::FOLD>;
+template <class O>
+using WithFold = OptX<typename O::Plain, O::WIDE, true>;
 
 // the compensated entries of COMP: x 0-1 (px, py), packed P 0-2 (P00, P10, P11)
 constexpr unsigned kKf6CXM = kPosCXM;
@@ -144,39 +161,55 @@ __device__ __forceinline__ void kf6_load_state(const float *xg, const float *Pg,
 // either way, for any Q, R and state.  Bits, not floats: -0.0 -> +0.0 and a NaN are written.
 // Structural planes only (not those that merely converge under one tuning), so a tick costs the
 // same at every step.  The cross planes are 3, 4, 8, 12, 15, 16, 18, 19 (P20 P21 P32 P42 P50 P51
-// P53 P54); the mask is their position half, P20 P21 P50 P51 (profiles/kf6_skip_store_ab.json).
+// P53 P54); the default mask is their position half, P20 P21 P50 P51 (profiles/kf6_skip_store_ab.json).
+// The mask is a template argument of everything below: an instantiation with Opt's WIDE trait
+// takes all eight (kKf6SkipWide), every other one the narrow default (kf6_mask).
 #ifndef FMSKF_KF6_SKIP_MASK
 #define FMSKF_KF6_SKIP_MASK ((1u << 3) | (1u << 4) | (1u << 15) | (1u << 16))
 #endif
 constexpr uint32_t kKf6SkipMask = FMSKF_KF6_SKIP_MASK;
-static_assert((kKf6SkipMask >> 21) == 0 && (kKf6SkipMask & (uint32_t)kKf6CPM) == 0,
+constexpr uint32_t kKf6SkipWide = kKf6SkipMask | (1u << 8) | (1u << 12) | (1u << 18) | (1u << 19);
+constexpr bool kf6_mask_ok(uint32_t m) { return (m >> 21) == 0 && (m & (uint32_t)kKf6CPM) == 0; }
+static_assert(kf6_mask_ok(kKf6SkipMask) && kf6_mask_ok(kKf6SkipWide),
               "packed P planes only, none of the compensated ones");
-constexpr int kKf6SkipN = __builtin_popcount(kKf6SkipMask);
-constexpr bool kf6_skip(int k) { return ((kKf6SkipMask >> k) & 1u) != 0; }
-constexpr int kf6_skip_slot(int k) { return __builtin_popcount(kKf6SkipMask & ((1u << k) - 1u)); }
+template <class O>
+constexpr uint32_t kf6_mask() {
+  return O::WIDE ? kKf6SkipWide : kKf6SkipMask;
+}
+template <uint32_t M>
+constexpr bool kf6_skip(int k) {
+  return ((M >> k) & 1u) != 0;
+}
+template <uint32_t M>
+constexpr int kf6_skip_slot(int k) {
+  return __builtin_popcount(M & ((1u << k) - 1u));
+}
 // the loaded bit patterns of the masked planes
+template <uint32_t M = kKf6SkipMask>
 struct Kf6Old {
-  uint32_t v[kKf6SkipN ? kKf6SkipN : 1];
+  static_assert(kf6_mask_ok(M), "packed P planes only, none of the compensated ones");
+  uint32_t v[__builtin_popcount(M) ? __builtin_popcount(M) : 1];
 };
-__device__ __forceinline__ Kf6Old kf6_keep_old(const float (&P)[21]) {
-  Kf6Old o;
+template <uint32_t M = kKf6SkipMask>
+__device__ __forceinline__ Kf6Old<M> kf6_keep_old(const float (&P)[21]) {
+  Kf6Old<M> o;
 #pragma unroll
   for (int k = 0; k < 21; k++)
-    if (kf6_skip(k)) o.v[kf6_skip_slot(k)] = __builtin_bit_cast(uint32_t, P[k]);
+    if (kf6_skip<M>(k)) o.v[kf6_skip_slot<M>(k)] = __builtin_bit_cast(uint32_t, P[k]);
   return o;
 }
 // plane k of P (k a constant once the callers' loops are unrolled): every lane, or for a masked
 // plane the lanes whose bits changed
-template <int SP>
+template <int SP, uint32_t M>
 __device__ __forceinline__ void kf6_st_p(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, int k, float v,
-                                         const Kf6Old &old) {
-  if (kf6_skip(k) && __builtin_bit_cast(uint32_t, v) == old.v[kf6_skip_slot(k)]) return;
+                                         const Kf6Old<M> &old) {
+  if (kf6_skip<M>(k) && __builtin_bit_cast(uint32_t, v) == old.v[kf6_skip_slot<M>(k)]) return;
   st_f32<SP>(r, voff, soff, v);
 }
 
-template <class O>
+template <class O, uint32_t M>
 __device__ __forceinline__ void kf6_store_state(float *xg, float *Pg, uint64_t, uint32_t i, const float (&x)[6],
-                                                const float (&P)[21], const Kf6Old &old) {
+                                                const float (&P)[21], const Kf6Old<M> &old) {
   constexpr int SP = st_pol(O::CP);
   constexpr uint32_t W = tile_w<float>();
   const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
