@@ -198,6 +198,58 @@ int fmskf_tick(fmskf_handle h, const fmskf_tick_inputs *in);
 int fmskf_tick_many(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
                     uint64_t tick_stride);
 
+/* ---- fixed-interval smoothing of a replayed window (KF6) ----------------------- */
+/* fmskf_tick_many returns a filter's answer: the state after the last tick.  The estimate a
+ * replayed log wants at tick t uses the measurements after t as well: the fixed-interval
+ * (Rauch-Tung-Striebel) smoother.  For KF6 it is exact and cheap: F and H are constant, and the
+ * measurement is rebuilt bit for bit from the recorded inputs.
+ *
+ * fmskf_tick_many_smooth takes the inputs of fmskf_tick_many (records or the three planes, an
+ * optional `valid` mask, host or device memory; explicit planes required) and does two things.
+ * 1. It advances the handle exactly as fmskf_tick_many(h, in, n_ticks, tick_stride) would: x, P
+ *    and every counter are bit for bit what that call leaves.
+ * 2. With, for tick t = 0 .. T-1, the prior (x-[t], P-[t]) = the state before the tick, the
+ *    filtered state (x+[t], P+[t]) = after the tick's measurement update (the prior where
+ *    valid == 0), and the prior of t+1 the predict of the filtered state, it writes for every t
+ *    the estimate of the state at tick t's measurement time given all T measurements:
+ *        x_s[T-1] = x+[T-1],  P_s[T-1] = P+[T-1]
+ *        C = P+[t] F^T (P-[t+1])^-1
+ *        x_s[t] = x+[t] + C (x_s[t+1] - x-[t+1]),  P_s[t] = P+[t] + C (P_s[t+1] - P-[t+1]) C^T
+ *    the heading difference wrapped as the innovation is wrapped, the output heading wrapped
+ *    into [-pi, pi).  The kernels form these numbers in fp32 by an equivalent recursion without
+ *    cancellation (C = F^-1 (I - Q (P-[t+1])^-1), csrc/smooth_lane.hpp), so a smoothed variance
+ *    stays positive while a robot's prior is still the diffuse P0; it needs P-[t+1] positive
+ *    definite.  tests/smooth_ref.py holds the float64 definition and the bound the fp32 results
+ *    are held to.
+ * Two launches: the ticks, storing every tick's prior (108 B per robot and tick) into a
+ * workspace the handle owns, then one backward pass.  The workspace only grows;
+ * fmskf_smooth_workspace_bytes is a pure query (at least 108 * N * n_ticks),
+ * fmskf_smooth_reserve allocates ahead of time so that a timed loop never allocates, and
+ * fmskf_smooth_reserve(h, 0) or fmskf_destroy frees it.  No checkpoint contains it.  Host outputs
+ * are staged on the device and copied out on the handle's stream; the call returns when they are
+ * complete.  Device outputs are asynchronous on the handle's stream.  fmskf_set_timing /
+ * fmskf_last_kernel_ms cover both passes.
+ *
+ * FMSKF_ENOTSUP: a model other than KF6, a handle with FMSKF_CFG_COMP_POS, a handle with a gate
+ * set (the accept / force decisions would have to be recorded per tick).  FMSKF_EINVAL: out or
+ * out->x NULL, reserved != 0, a bad mem flag, pitch non-zero and below N, n_ticks == 0,
+ * everything fmskf_tick_many refuses, a call inside a graph capture.  Each is raised before
+ * anything is launched, and the handle is untouched.  FMSKF_ENOMEM: the workspace or the output
+ * staging cannot be allocated; that happens before the first launch, so the state is untouched
+ * then too. */
+typedef struct fmskf_smooth_out {
+  uint32_t mem;       /* FMSKF_MEM_HOST or FMSKF_MEM_DEVICE for x and P */
+  uint32_t reserved;  /* must be 0 */
+  uint64_t pitch;     /* elements between consecutive rows; 0 = N, otherwise >= N */
+  float *x;           /* [T][6][pitch]  smoothed state of every tick; required */
+  float *P;           /* [T][21][pitch] smoothed covariance, packed like fmskf_get_state; NULL = not formed */
+} fmskf_smooth_out;
+
+int fmskf_tick_many_smooth(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
+                           uint64_t tick_stride, const fmskf_smooth_out *out);
+int fmskf_smooth_workspace_bytes(fmskf_handle h, uint32_t n_ticks, uint64_t *bytes);
+int fmskf_smooth_reserve(fmskf_handle h, uint32_t n_ticks);   /* grow-only; 0 frees */
+
 /* ---- chi-square innovation gate (KF6) ---------------------------------------- */
 /* Off by default: a handle that never sets a gate runs the kernels and computes the bits it
  * always did, and writes the checkpoints it always wrote.

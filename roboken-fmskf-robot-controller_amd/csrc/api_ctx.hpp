@@ -9,6 +9,7 @@
 //   api_fix.cpp         fmskf_correct_pose
 //   api_select.cpp      fmskf_select, fmskf_get_state_subset / fmskf_set_state_subset
 //   api_range.cpp       fmskf_set_anchors / fmskf_get_anchors, fmskf_correct_range
+//   api_smooth.cpp      fmskf_tick_many_smooth and its workspace
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -200,6 +201,11 @@ struct fmskf_ctx {
   // state: every call rewrites what it reads, and no checkpoint holds it.
   uint8_t *sel_flag = nullptr;
   uint32_t *sel_blk = nullptr, *sel_chunk = nullptr;
+  // fmskf_tick_many_smooth: the history of per-tick priors (api_smooth.cpp), grow-only, freed by
+  // fmskf_smooth_reserve(h, 0) and with the handle.  Not state: every call writes what it reads,
+  // and no checkpoint holds it.
+  void *smooth_ws = nullptr;
+  size_t smooth_ws_bytes = 0;
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
   // call) that ran as the tick, control-step and frame kernels instead of one fused kernel
@@ -337,6 +343,7 @@ struct fmskf_ctx {
     for (void *p : allocs) (void)hipFree(p);
     if (stage) (void)hipFree(stage);
     if (oscratch) (void)hipFree(oscratch);
+    if (smooth_ws) (void)hipFree(smooth_ws);
     for (int k = 0; k < 2; k++) {
       if (pin_in[k]) (void)hipHostFree(pin_in[k]);
       if (pin_ev[k]) (void)hipEventDestroy(pin_ev[k]);

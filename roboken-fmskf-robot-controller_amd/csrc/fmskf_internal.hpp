@@ -242,6 +242,19 @@ struct SubsetDev {
   unsigned long long *ignored;  // malformed entries (fmskf_get_counters [4])
   bool set;
 };
+// fmskf_tick_many_smooth (kernels_smooth.hip; argument structs of its own).  The history the
+// forward pass writes and the backward pass reads, in the handle's workspace: tick t's priors
+// tiled like the state, x [N/W][6][W] at x + t * sx and P [N/W][21][W] at P + t * sp (elements;
+// api_smooth.cpp keeps a tick's x and P tiles together, so sx == sp is the whole slice)
+struct SmoothHist {
+  float *x, *P;
+  uint64_t sx, sp;
+};
+// the caller's outputs (device pointers): x [T][6][pitch], P [T][21][pitch] or null
+struct SmoothOut {
+  float *x, *P;
+  uint64_t pitch;
+};
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -461,6 +474,12 @@ int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool lib
 // state only (no FMSKF_CFG_COMP_POS), no fused ensemble record
 int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,
                     bool pred, hipStream_t st);
+// the two passes of fmskf_tick_many_smooth (kernels_smooth.hip): the ticks of launch_kf6's
+// tick_many with the history store (plain ungated KF6 state only), then the backward recursion
+int launch_kf6_smooth_fwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,
+                          hipStream_t st);
+int launch_kf6_smooth_bwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,
+                          const SmoothOut &out, hipStream_t st);
 // the gate words unpacked into status [N], run [N], rejects [N] (device pointers, any may be null)
 int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
                        hipStream_t st);

@@ -80,6 +80,11 @@ class TickInputs(C.Structure):
     ]
 
 
+class SmoothOut(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("reserved", C.c_uint32), ("pitch", C.c_uint64), ("x", C.c_void_p),
+                ("P", C.c_void_p)]
+
+
 class Gate(C.Structure):
     _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
 
@@ -155,6 +160,9 @@ SIGNATURES = {
     "fmskf_predict": (C.c_int, [_H, C.POINTER(TickInputs)]),
     "fmskf_tick": (C.c_int, [_H, C.POINTER(TickInputs)]),
     "fmskf_tick_many": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64]),
+    "fmskf_tick_many_smooth": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(SmoothOut)]),
+    "fmskf_smooth_workspace_bytes": (C.c_int, [_H, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "fmskf_smooth_reserve": (C.c_int, [_H, C.c_uint32]),
     "fmskf_get_pose": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_vel": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_state": (C.c_int, [_H, _P, _P, C.c_uint32]),

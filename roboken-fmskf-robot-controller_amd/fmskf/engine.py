@@ -606,6 +606,68 @@ class Engine:
         ti, _keep = self._inputs(kw, n_ticks, stride)
         check(load().fmskf_tick_many(self.h, C.byref(ti), int(n_ticks), stride), "tick_many")
 
+    def tick_many_smooth(self, n_ticks, tick_stride=None, want_P=False, out_x=None, out_P=None, pitch=0, **kw):
+        """fmskf_tick_many_smooth (KF6): the ticks of tick_many, plus the fixed-interval
+        (Rauch-Tung-Striebel) smoothed state of every tick, x_s [T, 6, N], and with want_P (or
+        out_P) its covariance, P_s [T, 21, N] packed like get_state.  Returns x_s, or (x_s, P_s).
+        numpy inputs give numpy results; torch device inputs give torch device results,
+        asynchronous on the handle's stream.  out_x / out_P: the caller's C-contiguous float32
+        arrays [T, 6, pitch or N] / [T, 21, pitch or N] (numpy, or torch device tensors whatever
+        the inputs' memory); with pitch > N the elements past N of every row are left alone."""
+        T = int(n_ticks)
+        stride = self.n if tick_stride is None else int(tick_stride)
+        ti, keep = self._inputs(kw, T, stride)
+        cols = int(pitch) if pitch else self.n
+        if out_x is None and out_P is not None:
+            raise ValueError("tick_many_smooth: out_P without out_x")
+        want_P = bool(want_P) or out_P is not None
+        if out_x is None:
+            if keep.mem == MEM_DEVICE:
+                import torch
+                dev = keep.keep[0].device
+                mk = lambda r: torch.empty((T, r, cols), dtype=torch.float32, device=dev)
+            else:
+                mk = lambda r: np.empty((T, r, cols), np.float32)
+            out_x = mk(self.nx)
+        if want_P and out_P is None:
+            if _is_torch(out_x):
+                import torch
+                out_P = torch.empty((T, self.np_, cols), dtype=torch.float32, device=out_x.device)
+            else:
+                out_P = np.empty((T, self.np_, cols), np.float32)
+        so = _lib.SmoothOut()
+        for name, v, rows in (("out_x", out_x, self.nx), ("out_P", out_P, self.np_)):
+            if v is None:
+                continue
+            if tuple(v.shape) != (T, rows, cols):
+                raise ValueError(f"tick_many_smooth: {name} has shape {tuple(v.shape)}, want {(T, rows, cols)}")
+            if _is_torch(v):
+                if not v.is_cuda or not v.is_contiguous() or str(v.dtype) != "torch.float32":
+                    raise TypeError(f"tick_many_smooth: a torch {name} must be a contiguous float32 device tensor")
+            elif not isinstance(v, np.ndarray) or v.dtype != np.float32 or not v.flags.c_contiguous \
+                    or not v.flags.writeable:
+                raise TypeError(f"tick_many_smooth: a host {name} must be a writable C-contiguous float32 numpy array")
+        if out_P is not None and _is_torch(out_P) != _is_torch(out_x):
+            raise ValueError("tick_many_smooth: out_x and out_P must live in the same memory")
+        ptr = (lambda v: v.data_ptr()) if _is_torch(out_x) else (lambda v: v.ctypes.data)
+        so.mem = MEM_DEVICE if _is_torch(out_x) else MEM_HOST
+        so.pitch = int(pitch)
+        so.x = ptr(out_x)
+        so.P = ptr(out_P) if out_P is not None else None
+        check(load().fmskf_tick_many_smooth(self.h, C.byref(ti), T, stride, C.byref(so)), "tick_many_smooth")
+        return (out_x, out_P) if want_P else out_x
+
+    def smooth_workspace_bytes(self, n_ticks) -> int:
+        """fmskf_smooth_workspace_bytes: the history tick_many_smooth keeps for a window of n_ticks"""
+        b = C.c_uint64()
+        check(load().fmskf_smooth_workspace_bytes(self.h, int(n_ticks), C.byref(b)), "smooth_workspace_bytes")
+        return b.value
+
+    def smooth_reserve(self, n_ticks):
+        """fmskf_smooth_reserve: allocate the history of a window of n_ticks ahead of time (it only
+        grows); 0 frees it"""
+        check(load().fmskf_smooth_reserve(self.h, int(n_ticks)), "smooth_reserve")
+
     # ------------------------------------------------------------------ readout
     def get_state(self):
         x = np.empty((self.nx, self.n), self.dtype)
