@@ -621,7 +621,7 @@ int fmskf_select(fmskf_handle h, const fmskf_select_params *prm,
  * arrays.  With device pointers both calls are asynchronous on the handle's stream and can be
  * captured by fmskf_graph_begin; a host list inside a capture is FMSKF_EINVAL.  An array past
  * 4 GiB is reached through 64-bit lane addresses and non-temporal accesses, as in
- * fmskf_correct_pose; FMSKF_SUBSET_BIG=1 (read once, at the first launch) forces that form. */
+ * fmskf_correct_pose; FMSKF_LIST_BIG=1 (read once, at the first launch) forces that form. */
 int fmskf_get_state_subset(fmskf_handle h, const uint32_t *robots, uint64_t count,
                            float *x, float *p_packed, float *lo, uint32_t mem);
 int fmskf_set_state_subset(fmskf_handle h, const uint32_t *robots, uint64_t count,

@@ -454,6 +454,28 @@ void copy_planes_in(fmskf_ctx *h, void *dst, const void *src, size_t row, size_t
 void finish_out(fmskf_ctx *h, uint32_t mem);
 void *host_result(fmskf_ctx *h, size_t bytes);
 void copy_out_sync(fmskf_ctx *h, void *dst, const void *src, size_t bytes, uint32_t mem);
+// the models of the calls that work on a list of robots -- KF6 (plain, FMSKF_CFG_COMP_POS) and plain
+// EKF9 -- or FMSKF_ENOTSUP "<what> for KF6 ... and plain EKF9" (what: "pose fixes are", ...)
+void check_list_model(const fmskf_ctx *h, const char *what);
+// The per-entry outputs of fmskf_correct_pose / fmskf_correct_range: the caller's value [count]
+// (NIS, d2) and status [count], either may be null.  `value` and `status` are what the kernel
+// writes: the caller's own device pointers, or for host memory the two parts of one result buffer
+// (the pinned output slot when it fits, so the kernel writes them over PCIe, else device scratch).
+// deliver(), after the launch, brings a host result to the caller once the stream has drained.
+struct EntryOut {
+  float *value = nullptr;
+  uint8_t *status = nullptr;
+  EntryOut(fmskf_ctx *h, float *value, uint8_t *status, uint64_t count, uint32_t mem);
+  void deliver();
+
+ private:
+  fmskf_ctx *h;
+  float *user_value;
+  uint8_t *user_status;
+  size_t count;
+  uint32_t mem;
+  char *res = nullptr;
+};
 // api_comm.cpp
 double *ens_fold_dst(const fmskf_ctx *h, const fmskf_ctx::EnsSlot &S);
 void ens_fold_queued(fmskf_ctx *h, fmskf_ctx::EnsSlot &S);

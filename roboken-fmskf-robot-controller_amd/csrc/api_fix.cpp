@@ -11,10 +11,7 @@ int fmskf_correct_pose(fmskf_handle h, const fmskf_pose_fix *fixes, uint64_t cou
                        const fmskf_pose_fix_params *prm, float *nis, uint8_t *status, uint32_t mem) {
   return guarded([&] {
     check_handle(h);
-    const uint32_t model = h->cfg.model;
-    const bool comp = (h->cfg.flags & FMSKF_CFG_COMP_POS) != 0;
-    if ((model != FMSKF_MODEL_KF6 && model != FMSKF_MODEL_EKF9) || (model == FMSKF_MODEL_EKF9 && comp))
-      fail(FMSKF_ENOTSUP, "pose fixes are for KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9");
+    check_list_model(h, "pose fixes are");
     if (!prm) fail(FMSKF_EINVAL, "null fix parameters");
     if (prm->flags & ~FMSKF_FIX_HEADING) fail(FMSKF_EINVAL, "unknown FMSKF_FIX_* flags");
     const uint32_t m = (prm->flags & FMSKF_FIX_HEADING) ? 3u : 2u;
@@ -51,26 +48,13 @@ int fmskf_correct_pose(fmskf_handle h, const fmskf_pose_fix *fixes, uint64_t cou
     sg.add(&list, (size_t)count * sizeof(fmskf_pose_fix));
     sg.run();
     f.fixes = (const uint32_t *)list;
-    // host outputs: nis [count] then status [count] in one result buffer (the pinned output slot
-    // when it fits, so the kernel writes them over PCIe), copied out once the stream has drained
-    char *res = nullptr;
-    if (host && (nis || status)) res = (char *)host_result(h, (size_t)count * 5);
-    f.nis = host ? (nis ? (float *)res : nullptr) : nis;
-    f.status = host ? (status ? (uint8_t *)res + (size_t)count * 4 : nullptr) : status;
+    EntryOut out(h, nis, status, count, mem);
+    f.nis = out.value;
+    f.status = out.status;
     h->time_begin();
     launch_check(launch_pose_fix(h->s, f, h->stream), "pose fix kernel launch");
     h->time_end();
-    if (res) {
-      if (h->pin_out && res == fmskf_ctx::dev_ptr(h->pin_out)) {
-        hip_check(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
-        if (nis) memcpy(nis, h->pin_out, (size_t)count * 4);
-        if (status) memcpy(status, (char *)h->pin_out + (size_t)count * 4, (size_t)count);
-      } else {
-        copy_out(h, nis, res, (size_t)count * 4, mem);
-        copy_out(h, status, res + (size_t)count * 4, (size_t)count, mem);
-        finish_out(h, mem);
-      }
-    }
+    out.deliver();
   });
 }
 

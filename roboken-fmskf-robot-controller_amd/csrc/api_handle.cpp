@@ -429,6 +429,33 @@ void copy_out_sync(fmskf_ctx *h, void *dst, const void *src, size_t bytes, uint3
   finish_out(h, mem);
 }
 
+void check_list_model(const fmskf_ctx *h, const char *what) {
+  const uint32_t model = h->cfg.model;
+  const bool comp = (h->cfg.flags & FMSKF_CFG_COMP_POS) != 0;
+  if ((model != FMSKF_MODEL_KF6 && model != FMSKF_MODEL_EKF9) || (model == FMSKF_MODEL_EKF9 && comp))
+    fail(FMSKF_ENOTSUP, std::string(what) + " for KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9");
+}
+
+EntryOut::EntryOut(fmskf_ctx *hh, float *v, uint8_t *s, uint64_t n, uint32_t m)
+    : value(v), status(s), h(hh), user_value(v), user_status(s), count((size_t)n), mem(m) {
+  if (mem != FMSKF_MEM_HOST || (!v && !s)) return;
+  res = (char *)host_result(h, count * 5);
+  value = v ? (float *)res : nullptr;
+  status = s ? (uint8_t *)res + count * 4 : nullptr;
+}
+void EntryOut::deliver() {
+  if (!res) return;
+  if (h->pin_out && res == fmskf_ctx::dev_ptr(h->pin_out)) {
+    hip_check(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
+    if (user_value) memcpy(user_value, h->pin_out, count * 4);
+    if (user_status) memcpy(user_status, (char *)h->pin_out + count * 4, count);
+  } else {
+    copy_out(h, user_value, res, count * 4, mem);
+    copy_out(h, user_status, res + count * 4, count, mem);
+    finish_out(h, mem);
+  }
+}
+
 }  // namespace capi
 }  // namespace fmskf
 

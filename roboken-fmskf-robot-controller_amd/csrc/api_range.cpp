@@ -6,18 +6,6 @@
 using namespace fmskf;
 using namespace fmskf::capi;
 
-namespace {
-
-// KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9: the models of fmskf_correct_pose
-void check_range_model(const fmskf_ctx *h) {
-  const uint32_t model = h->cfg.model;
-  const bool comp = (h->cfg.flags & FMSKF_CFG_COMP_POS) != 0;
-  if ((model != FMSKF_MODEL_KF6 && model != FMSKF_MODEL_EKF9) || (model == FMSKF_MODEL_EKF9 && comp))
-    fail(FMSKF_ENOTSUP, "range updates are for KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9");
-}
-
-}  // namespace
-
 extern "C" {
 
 int fmskf_set_anchors(fmskf_handle h, const float *xyz, uint32_t count) {
@@ -60,7 +48,7 @@ int fmskf_correct_range(fmskf_handle h, const fmskf_range_fix *fixes, uint64_t c
                         const fmskf_range_params *prm, float *d2, uint8_t *status, uint32_t mem) {
   return guarded([&] {
     check_handle(h);
-    check_range_model(h);
+    check_list_model(h, "range updates are");
     if (!prm) fail(FMSKF_EINVAL, "null range parameters");
     if (prm->flags || prm->reserved) fail(FMSKF_EINVAL, "range flags and reserved must be 0");
     if (!isfinite(prm->var_m2) || !(prm->var_m2 > 0.0f)) fail(FMSKF_EINVAL, "var_m2 must be finite and > 0");
@@ -103,26 +91,13 @@ int fmskf_correct_range(fmskf_handle h, const fmskf_range_fix *fixes, uint64_t c
     sg.add(&list, (size_t)count * sizeof(fmskf_range_fix));
     sg.run();
     f.fixes = (const uint32_t *)list;
-    // host outputs: d2 [count] then status [count] in one result buffer (the pinned output slot
-    // when it fits), copied out once the stream has drained -- as fmskf_correct_pose stages them
-    char *res = nullptr;
-    if (host && (d2 || status)) res = (char *)host_result(h, (size_t)count * 5);
-    f.d2 = host ? (d2 ? (float *)res : nullptr) : d2;
-    f.status = host ? (status ? (uint8_t *)res + (size_t)count * 4 : nullptr) : status;
+    EntryOut out(h, d2, status, count, mem);
+    f.d2 = out.value;
+    f.status = out.status;
     h->time_begin();
     launch_check(launch_range_fix(h->s, f, h->cfg.trig == FMSKF_TRIG_LIBM, h->stream), "range kernel launch");
     h->time_end();
-    if (res) {
-      if (h->pin_out && res == fmskf_ctx::dev_ptr(h->pin_out)) {
-        hip_check(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
-        if (d2) memcpy(d2, h->pin_out, (size_t)count * 4);
-        if (status) memcpy(status, (char *)h->pin_out + (size_t)count * 4, (size_t)count);
-      } else {
-        copy_out(h, d2, res, (size_t)count * 4, mem);
-        copy_out(h, status, res + (size_t)count * 4, (size_t)count, mem);
-        finish_out(h, mem);
-      }
-    }
+    out.deliver();
   });
 }
 

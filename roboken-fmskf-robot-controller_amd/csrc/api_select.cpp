@@ -8,19 +8,11 @@ using namespace fmskf::capi;
 
 namespace {
 
-// KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9: the models of fmskf_correct_pose
-void check_list_model(fmskf_ctx *h, const char *what) {
-  const uint32_t model = h->cfg.model;
-  const bool comp = (h->cfg.flags & FMSKF_CFG_COMP_POS) != 0;
-  if ((model != FMSKF_MODEL_KF6 && model != FMSKF_MODEL_EKF9) || (model == FMSKF_MODEL_EKF9 && comp))
-    fail(FMSKF_ENOTSUP, std::string(what) + " is for KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9");
-}
-
 // the checks and the launch shared by the subset get and set; x / p / lo are the caller's
 void state_subset(fmskf_ctx *h, const uint32_t *robots, uint64_t count, const float *x, const float *p,
                   const float *lo, uint32_t mem, bool set) {
   check_handle(h);
-  check_list_model(h, set ? "fmskf_set_state_subset" : "fmskf_get_state_subset");
+  check_list_model(h, set ? "fmskf_set_state_subset is" : "fmskf_get_state_subset is");
   if (mem != FMSKF_MEM_HOST && mem != FMSKF_MEM_DEVICE) fail(FMSKF_EINVAL, "bad mem flag");
   const uint32_t lrows = h->s.thlo ? 1u : h->s.xlo ? kKf6LoRows : 0u;
   if (lo && !lrows) fail(FMSKF_EINVAL, "this model keeps no low-part rows");
@@ -88,7 +80,7 @@ int fmskf_select(fmskf_handle h, const fmskf_select_params *prm, uint32_t *robot
                  uint64_t capacity, uint64_t *count, uint32_t mem) {
   return guarded([&] {
     check_handle(h);
-    check_list_model(h, "fmskf_select");
+    check_list_model(h, "fmskf_select is");
     if (!prm) fail(FMSKF_EINVAL, "null select parameters");
     const uint32_t all = FMSKF_SEL_NONFINITE | FMSKF_SEL_POS_VAR | FMSKF_SEL_GATE_RUN;
     if ((prm->criteria & ~all) || !(prm->criteria & all)) fail(FMSKF_EINVAL, "criteria: FMSKF_SEL_* bits, at least one");

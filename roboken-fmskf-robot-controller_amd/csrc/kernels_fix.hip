@@ -54,9 +54,9 @@ struct MdFix {
 // NX: 6 (KF6) or 9 (EKF9, with the heading low part); MM: 2 or 3; COMP: KF6's position low parts
 template <int NX, int MM, bool COMP, int CP, bool BIG>
 __global__ __launch_bounds__(kBlock) void k_fix(FixArgs a) {
-  constexpr int NP = NX * (NX + 1) / 2;
-  constexpr bool EKF = NX == 9;
-  static_assert(!(EKF && COMP), "EKF9 with FMSKF_CFG_COMP_POS is not supported");
+  using S = ListRows<NX, COMP, CP, BIG>;
+  constexpr int NP = S::NP;
+  constexpr bool EKF = S::EKF;
   using Md = MdFix<NX, MM>;
   const uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
   const bool have = k < a.count;
@@ -74,22 +74,18 @@ __global__ __launch_bounds__(kBlock) void k_fix(FixArgs a) {
   float nis = 0.f;
   uint32_t status = FMSKF_FIX_IGNORED;
   if (ok) {
-    const FixRows<NX, CP, BIG> tx(a.x, a.pitch, robot);
-    const FixRows<NP, CP, BIG> tp(a.P, a.pitch, robot);
-    const FixRows<COMP ? (int)kKf6LoRows : 1, CP, BIG> tl(COMP ? a.lo : a.x, a.pitch, robot);
-    float x[NX], P[NP], cl[COMP ? kKf6LoRows : 1] = {}, lo = 0.f;
+    const S rows(a, robot);
+    float x[NX], P[NP], cl[S::NL] = {}, lo = 0.f;
+    // gather and scatter stay loops of the kernel's own (list_rows.hpp ListRows)
 #pragma unroll
-    for (int j = 0; j < NX; j++) x[j] = tx.ld(j);
+    for (int j = 0; j < NX; j++) x[j] = rows.tx.ld(j);
 #pragma unroll
-    for (int j = 0; j < NP; j++) P[j] = tp.ld(j);
+    for (int j = 0; j < NP; j++) P[j] = rows.tp.ld(j);
     if constexpr (COMP) {
 #pragma unroll
-      for (int j = 0; j < (int)kKf6LoRows; j++) cl[j] = tl.ld(j);
+      for (int j = 0; j < S::NL; j++) cl[j] = rows.tl.ld(j);
     }
-    if constexpr (EKF) {
-      if constexpr (BIG) lo = __builtin_nontemporal_load(a.thlo + robot);
-      else lo = ld_f32<CP>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0);
-    }
+    if constexpr (EKF) lo = rows.th.ld();
     // y = z - H x: a compensated state is hi + lo (as the EKF9's own heading innovation), the
     // heading innovation wrapped
     float y[MM], U[MM][NX], dinv[MM], w[MM];
@@ -110,17 +106,14 @@ __global__ __launch_bounds__(kBlock) void k_fix(FixArgs a) {
         kf_update_apply<Md, -1, float, NX, MM, NP>(x, P, U, dinv, w);
       }
 #pragma unroll
-      for (int j = 0; j < NX; j++) tx.st(j, x[j]);
+      for (int j = 0; j < NX; j++) rows.tx.st(j, x[j]);
 #pragma unroll
-      for (int j = 0; j < NP; j++) tp.st(j, P[j]);
+      for (int j = 0; j < NP; j++) rows.tp.st(j, P[j]);
       if constexpr (COMP) {
 #pragma unroll
-        for (int j = 0; j < (int)kKf6LoRows; j++) tl.st(j, cl[j]);
+        for (int j = 0; j < S::NL; j++) rows.tl.st(j, cl[j]);
       }
-      if constexpr (EKF) {
-        if constexpr (BIG) __builtin_nontemporal_store(lo, a.thlo + robot);
-        else st_f32<st_pol(CP)>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0, lo);
-      }
+      if constexpr (EKF) rows.th.st(lo);
       nan_guard(x, P, a.counters);
     }
   }
@@ -128,40 +121,22 @@ __global__ __launch_bounds__(kBlock) void k_fix(FixArgs a) {
     if (a.nis) a.nis[k] = nis;
     if (a.status) a.status[k] = (uint8_t)status;
   }
-  const unsigned long long bad = __ballot(have && !ok);
-  if (bad && (threadIdx.x & 63) == __builtin_ctzll(bad)) atomicAdd(a.ignored, (unsigned long long)__popcll(bad));
-}
-
-template <int NX, int MM, bool COMP>
-static void launch_fix_m(const FixArgs &a, bool nt, bool big, hipStream_t st) {
-  const dim3 g = grid_for(a.count);
-  if (big) k_fix<NX, MM, COMP, kStateNT, true><<<g, kBlock, 0, st>>>(a);
-  else if (nt) k_fix<NX, MM, COMP, kStateNT, false><<<g, kBlock, 0, st>>>(a);
-  else k_fix<NX, MM, COMP, 0, false><<<g, kBlock, 0, st>>>(a);
+  count_ignored(have && !ok, a.ignored);
 }
 
 int launch_pose_fix(const DevState &s, const PoseFixDev &f, hipStream_t st) {
-  if (s.tile != tile_w<float>()) return (int)hipErrorNotSupported;
+  const ListRegime rg = list_regime(s);
+  if (!rg.ok) return (int)hipErrorNotSupported;
   if (!f.fixes || !f.count || !f.ignored || (f.m != 2 && f.m != 3)) return (int)hipErrorInvalidValue;
-  const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
-  if ((!ekf && s.model != FMSKF_MODEL_KF6) || (ekf && (comp || !s.thlo))) return (int)hipErrorNotSupported;
   FixArgs a{s.n, f.count, s.pitch, (float *)s.x, (float *)s.P, s.thlo, s.xlo, f.fixes, f.nis, f.status,
             s.counters, f.ignored, {}, f.nis_max};
   for (int k = 0; k < 6; k++) a.r[k] = f.r[k];
-  // the state's cache policy as the model's tick launcher chooses it
-  const bool nt = state_nt(ekf ? s.n * 55 * 4 : s.n * (comp ? 128 : 108));
-  // the largest array (P) within reach of a 32-bit byte offset?
-  const bool big = rows_big(ekf, s.pitch);
-  if (ekf) {
-    if (f.m == 3) launch_fix_m<9, 3, false>(a, nt, big, st);
-    else launch_fix_m<9, 2, false>(a, nt, big, st);
-  } else if (comp) {
-    if (f.m == 3) launch_fix_m<6, 3, true>(a, nt, big, st);
-    else launch_fix_m<6, 2, true>(a, nt, big, st);
-  } else {
-    if (f.m == 3) launch_fix_m<6, 3, false>(a, nt, big, st);
-    else launch_fix_m<6, 2, false>(a, nt, big, st);
-  }
+  with_list_regime(
+      rg,
+      [&](auto NX, auto COMP, auto CP, auto BIG, auto M3) {
+        k_fix<NX(), M3() ? 3 : 2, COMP(), CP(), BIG()><<<grid_for(a.count), kBlock, 0, st>>>(a);
+      },
+      f.m == 3);
   return (int)hipGetLastError();
 }
 

@@ -57,9 +57,8 @@ __device__ __forceinline__ void range_out(const RangeArgs &a, uint64_t k, float 
 // handle's sin / cos policy
 template <int NX, bool COMP, bool LIBM, int CP, bool BIG>
 __global__ __launch_bounds__(kBlock) void k_range(RangeArgs a) {
-  constexpr int NP = NX * (NX + 1) / 2;
-  constexpr bool EKF = NX == 9;
-  static_assert(!(EKF && COMP), "EKF9 with FMSKF_CFG_COMP_POS is not supported");
+  using S = ListRows<NX, COMP, CP, BIG>;
+  constexpr bool EKF = S::EKF;
   constexpr int CI = EKF ? 2 : -1;
   constexpr unsigned CXM = COMP ? kKf6CXM : 0u;
   constexpr unsigned long long CPM = COMP ? kKf6CPM : 0ull;
@@ -85,22 +84,18 @@ __global__ __launch_bounds__(kBlock) void k_range(RangeArgs a) {
       nign++;
     }
   } else {
-    const FixRows<NX, CP, BIG> tx(a.x, a.pitch, robot);
-    const FixRows<NP, CP, BIG> tp(a.P, a.pitch, robot);
-    const FixRows<COMP ? (int)kKf6LoRows : 1, CP, BIG> tl(COMP ? a.lo : a.x, a.pitch, robot);
-    float x[NX], P[NP], cl[COMP ? kKf6LoRows : 1] = {}, lo = 0.f;
+    const S rows(a, robot);
+    float x[NX], P[S::NP], cl[S::NL] = {}, lo = 0.f;
+    // gather and scatter stay loops of the kernel's own (list_rows.hpp ListRows)
 #pragma unroll
-    for (int j = 0; j < NX; j++) x[j] = tx.ld(j);
+    for (int j = 0; j < NX; j++) x[j] = rows.tx.ld(j);
 #pragma unroll
-    for (int j = 0; j < NP; j++) P[j] = tp.ld(j);
+    for (int j = 0; j < S::NP; j++) P[j] = rows.tp.ld(j);
     if constexpr (COMP) {
 #pragma unroll
-      for (int j = 0; j < (int)kKf6LoRows; j++) cl[j] = tl.ld(j);
+      for (int j = 0; j < S::NL; j++) cl[j] = rows.tl.ld(j);
     }
-    if constexpr (EKF) {
-      if constexpr (BIG) lo = __builtin_nontemporal_load(a.thlo + robot);
-      else lo = ld_f32<CP>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0);
-    }
+    if constexpr (EKF) lo = rows.th.ld();
     bool any = false;
 #pragma unroll 1
     for (int j = 0; j < kRunMax; j++) {
@@ -133,54 +128,33 @@ __global__ __launch_bounds__(kBlock) void k_range(RangeArgs a) {
     }
     if (any) {
 #pragma unroll
-      for (int j = 0; j < NX; j++) tx.st(j, x[j]);
+      for (int j = 0; j < NX; j++) rows.tx.st(j, x[j]);
 #pragma unroll
-      for (int j = 0; j < NP; j++) tp.st(j, P[j]);
+      for (int j = 0; j < S::NP; j++) rows.tp.st(j, P[j]);
       if constexpr (COMP) {
 #pragma unroll
-        for (int j = 0; j < (int)kKf6LoRows; j++) tl.st(j, cl[j]);
+        for (int j = 0; j < S::NL; j++) rows.tl.st(j, cl[j]);
       }
-      if constexpr (EKF) {
-        if constexpr (BIG) __builtin_nontemporal_store(lo, a.thlo + robot);
-        else st_f32<st_pol(CP)>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0, lo);
-      }
+      if constexpr (EKF) rows.th.st(lo);
       nan_guard(x, P, a.counters);
     }
   }
   if (nign) atomicAdd(a.ignored, (unsigned long long)nign);  // malformed lists only
 }
 
-template <int NX, bool COMP>
-static void launch_range_m(const RangeArgs &a, bool libm, bool nt, bool big, hipStream_t st) {
-  const dim3 g = grid_for(a.count);
-  with_bools(
-      [&](auto lm) {
-        if (big) k_range<NX, COMP, lm(), kStateNT, true><<<g, kBlock, 0, st>>>(a);
-        else if (nt) k_range<NX, COMP, lm(), kStateNT, false><<<g, kBlock, 0, st>>>(a);
-        else k_range<NX, COMP, lm(), 0, false><<<g, kBlock, 0, st>>>(a);
-      },
-      libm);
-}
-
 int launch_range_fix(const DevState &s, const RangeDev &f, bool libm, hipStream_t st) {
-  if (s.tile != tile_w<float>()) return (int)hipErrorNotSupported;
+  const ListRegime rg = list_regime(s);
+  if (!rg.ok) return (int)hipErrorNotSupported;
   if (!f.fixes || !f.count || !f.ignored || !f.anchors || !f.n_anchors) return (int)hipErrorInvalidValue;
-  const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
-  if ((!ekf && s.model != FMSKF_MODEL_KF6) || (ekf && (comp || !s.thlo))) return (int)hipErrorNotSupported;
   RangeArgs a{s.n, f.count, s.pitch, (float *)s.x, (float *)s.P, s.thlo, s.xlo, f.fixes, f.anchors, s.sintab,
               f.d2, f.status, s.counters, f.ignored, f.n_anchors, {f.tag[0], f.tag[1], f.tag[2]},
               f.var, f.d2_max, f.d_min};
-  // FMSKF_RANGE_BIG=1 forces the 64-bit-address form an array past 4 GiB needs
-  static const bool force_big = [] {
-    const char *e = getenv("FMSKF_RANGE_BIG");
-    return e && atoi(e) != 0;
-  }();
-  // the state's cache policy as the model's tick launcher chooses it (launch_pose_fix)
-  const bool nt = state_nt(ekf ? s.n * 55 * 4 : s.n * (comp ? 128 : 108));
-  const bool big = force_big || rows_big(ekf, s.pitch);
-  if (ekf) launch_range_m<9, false>(a, libm, nt, big, st);
-  else if (comp) launch_range_m<6, true>(a, libm, nt, big, st);
-  else launch_range_m<6, false>(a, libm, nt, big, st);
+  with_list_regime(
+      rg,
+      [&](auto NX, auto COMP, auto CP, auto BIG, auto LIBM) {
+        k_range<NX(), COMP(), LIBM(), CP(), BIG()><<<grid_for(a.count), kBlock, 0, st>>>(a);
+      },
+      libm);
   return (int)hipGetLastError();
 }
 

@@ -179,27 +179,16 @@ static void launch_flag(const SelArgs &a, hipStream_t st) {
   }
 }
 
-// KF6 (plain, FMSKF_CFG_COMP_POS) and plain EKF9 with the tiled state
-static bool list_model(const DevState &s) {
-  if (s.tile != tile_w<float>()) return false;
-  const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
-  return (ekf || s.model == FMSKF_MODEL_KF6) && !(ekf && (comp || !s.thlo));
-}
-// the state's cache policy as the model's tick launcher chooses it
-static bool list_nt(const DevState &s) {
-  return state_nt(s.model == FMSKF_MODEL_EKF9 ? s.n * 55 * 4 : s.n * (s.xlo ? 128 : 108));
-}
-
 int launch_select(const DevState &s, const SelectDev &d, hipStream_t st) {
-  if (!list_model(s)) return (int)hipErrorNotSupported;
-  const bool ekf = s.model == FMSKF_MODEL_EKF9;
+  const ListRegime rg = list_regime(s);
+  if (!rg.ok) return (int)hipErrorNotSupported;
+  const bool ekf = rg.ekf, nt = rg.nt;
   if (!d.flag || !d.blk || !d.chunk || !d.count || (d.capacity && !d.robots)) return (int)hipErrorInvalidValue;
   if ((d.criteria & FMSKF_SEL_GATE_RUN) && !(ekf ? (const void *)d.rowgate_word : (const void *)d.gate_word))
     return (int)hipErrorInvalidValue;
   SelArgs a{s.n, (float *)s.x, (float *)s.P, d, 0, 0};
   a.nb = grid_for(s.n).x;
   a.nc = (a.nb + kSelChunk - 1) / kSelChunk;
-  const bool nt = list_nt(s);
   if (ekf) nt ? launch_flag<9, kStateNT>(a, st) : launch_flag<9, 0>(a, st);
   else nt ? launch_flag<6, kStateNT>(a, st) : launch_flag<6, 0>(a, st);
   k_sel_chunks<<<a.nc, kBlock, 0, st>>>(a);
@@ -275,44 +264,27 @@ __global__ __launch_bounds__(kBlock) void k_subset(SubArgs a) {
     if constexpr (EKF) {
       // set: a given x restarts the heading low part at 0, a given lo replaces that
       if (SET ? (ux || ul) : ul != nullptr) {
-        if constexpr (SET) {
-          const float v = ul ? *ul : 0.f;
-          if constexpr (BIG) __builtin_nontemporal_store(v, a.thlo + robot);
-          else st_f32<st_pol(CP)>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0, v);
-        } else {
-          if constexpr (BIG) *ul = __builtin_nontemporal_load(a.thlo + robot);
-          else *ul = ld_f32<CP>(rsrc(a.thlo, a.n * sizeof(float)), robot * 4u, 0);
-        }
+        const ThLo<CP, BIG> th{a.thlo, a.n, robot};
+        if constexpr (SET) th.st(ul ? *ul : 0.f);
+        else *ul = th.ld();
       }
     }
   }
-  const unsigned long long bad = __ballot(have && !ok);
-  if (bad && (threadIdx.x & 63) == __builtin_ctzll(bad)) atomicAdd(a.d.ignored, (unsigned long long)__popcll(bad));
-}
-
-template <int NX, bool COMP, bool SET>
-static void launch_subset_m(const SubArgs &a, bool nt, bool big, hipStream_t st) {
-  const dim3 g = grid_for(a.d.count);
-  if (big) k_subset<NX, COMP, kStateNT, true, SET><<<g, kBlock, 0, st>>>(a);
-  else if (nt) k_subset<NX, COMP, kStateNT, false, SET><<<g, kBlock, 0, st>>>(a);
-  else k_subset<NX, COMP, 0, false, SET><<<g, kBlock, 0, st>>>(a);
+  count_ignored(have && !ok, a.d.ignored);
 }
 
 int launch_state_subset(const DevState &s, const SubsetDev &d, hipStream_t st) {
-  if (!list_model(s)) return (int)hipErrorNotSupported;
+  const ListRegime rg = list_regime(s);
+  if (!rg.ok) return (int)hipErrorNotSupported;
   if (!d.robots || !d.count || !d.ignored) return (int)hipErrorInvalidValue;
-  const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
-  if (d.lo && !ekf && !comp) return (int)hipErrorInvalidValue;
+  if (d.lo && !rg.ekf && !rg.comp) return (int)hipErrorInvalidValue;
   const SubArgs a{s.n, s.pitch, (float *)s.x, (float *)s.P, s.thlo, s.xlo, d};
-  // FMSKF_SUBSET_BIG=1 forces the 64-bit-address form an array past 4 GiB needs
-  static const bool force_big = [] {
-    const char *e = getenv("FMSKF_SUBSET_BIG");
-    return e && atoi(e) != 0;
-  }();
-  const bool nt = list_nt(s), big = force_big || rows_big(ekf, s.pitch);
-  if (ekf) d.set ? launch_subset_m<9, false, true>(a, nt, big, st) : launch_subset_m<9, false, false>(a, nt, big, st);
-  else if (comp) d.set ? launch_subset_m<6, true, true>(a, nt, big, st) : launch_subset_m<6, true, false>(a, nt, big, st);
-  else d.set ? launch_subset_m<6, false, true>(a, nt, big, st) : launch_subset_m<6, false, false>(a, nt, big, st);
+  with_list_regime(
+      rg,
+      [&](auto NX, auto COMP, auto CP, auto BIG, auto SET) {
+        k_subset<NX(), COMP(), CP(), BIG(), SET()><<<grid_for(a.d.count), kBlock, 0, st>>>(a);
+      },
+      d.set);
   return (int)hipGetLastError();
 }
 

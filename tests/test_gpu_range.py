@@ -381,10 +381,10 @@ def child_main(path):
     print("range forms ok")
 
 
-@pytest.mark.parametrize("var", ["FMSKF_STATE_NT", "FMSKF_RANGE_BIG"])
+@pytest.mark.parametrize("var", ["FMSKF_STATE_NT", "FMSKF_LIST_BIG"])
 def test_forms_in_a_fresh_process(tmp_path, var):
     """the same calls with FMSKF_STATE_NT=1 (the streamed-state cache policy) and with
-    FMSKF_RANGE_BIG=1 (64-bit lane addresses, the form an array past 4 GiB takes), each in a fresh
+    FMSKF_LIST_BIG=1 (64-bit lane addresses, the form an array past 4 GiB takes), each in a fresh
     process (the variables are read once, at the first launch): bit for bit the host form's state,
     d2 and status, for every key"""
     path = str(tmp_path / "forms.npz")

@@ -452,13 +452,13 @@ def test_subset_get_set(key):
 
 
 def test_subset_get_set_64bit_addresses():
-    """the same checks with FMSKF_SUBSET_BIG=1, the form an array past 4 GiB takes, in a fresh
+    """the same checks with FMSKF_LIST_BIG=1, the form an array past 4 GiB takes, in a fresh
     process (the variable is read at the first launch)"""
     code = ("import sys; sys.path[:0] = %r\nimport test_gpu_select as t\n"
             "for key in t.KEYS:\n    t.subset_checks(key)\nprint('subset checks ok')\n"
             % [os.path.join(ROOT, "tests"), ROOT, os.path.join(ROOT, "roboken-fmskf-robot-controller_amd")])
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, FMSKF_SUBSET_BIG="1"))
+                         env=dict(os.environ, FMSKF_LIST_BIG="1"))
     assert out.returncode == 0 and "subset checks ok" in out.stdout, out.stdout + out.stderr
 
 
