@@ -56,13 +56,7 @@ void ens_carry_launched(fmskf_ctx *h, fmskf_ctx::EnsSlot *C, const TickIn &t) {
 }
 // FMSKF_ENS_CARRY_PLAIN=0 (read once): a plain tick carries no fold; the event's fold runs
 // stand-alone ahead of it, as ahead of every other call (the tests' and the A/B's reference)
-bool ens_carry_plain() {
-  static const bool on = [] {
-    const char *e = getenv("FMSKF_ENS_CARRY_PLAIN");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
+bool ens_carry_plain() { return FMSKF_ENV_INT("FMSKF_ENS_CARRY_PLAIN", 1) != 0; }
 // the stand-alone fold of the newest event, when no tick kernel carried it
 void ens_flush(fmskf_ctx *h) {
   if (h->ens_carry < 0) return;
@@ -228,10 +222,7 @@ void fmskf::capi::ens_gather_async(fmskf_ctx *h, fmskf_ctx::EnsSlot &S) {
   const uint32_t nx = h->d.nx, len = 1 + nx + nx * (nx + 1) / 2;
   // FMSKF_ENS_XTIME=0: no timing events around the exchange (A/B of their cost; then
   // fmskf_ensemble_exchange_ms reports -1)
-  static const bool xtime = [] {
-    const char *e = getenv("FMSKF_ENS_XTIME");
-    return !e || atoi(e) != 0;
-  }();
+  const bool xtime = FMSKF_ENV_INT("FMSKF_ENS_XTIME", 1) != 0;
   if (xtime && !S.x0) {  // timing events on the side stream only (the tick stream records none)
     hip_check(hipEventCreate(&S.x0), "hipEventCreate");
     hip_check(hipEventCreate(&S.x1), "hipEventCreate");

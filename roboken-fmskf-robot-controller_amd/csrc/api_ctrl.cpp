@@ -203,21 +203,8 @@ int fmskf_can_tx(fmskf_handle h, uint8_t *frames, uint32_t mem) {
 
 // FMSKF_ISR_FUSED=0: the KF6 and EKF9 ISRs as three kernels (A/B, and the tests' cross-check)
 // FMSKF_RS_PREV_SKIP=0: the fused RS CAN ISR always reads and writes the prev planes (A/B)
-static bool rs_prev_skip() {
-  static const bool v = [] {
-    const char *e = getenv("FMSKF_RS_PREV_SKIP");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
-
-static bool isr_kf6_fused() {
-  static const bool v = [] {
-    const char *e = getenv("FMSKF_ISR_FUSED");
-    return !e || atoi(e) != 0;
-  }();
-  return v;
-}
+static bool rs_prev_skip() { return FMSKF_ENV_INT("FMSKF_RS_PREV_SKIP", 1) != 0; }
+static bool isr_kf6_fused() { return FMSKF_ENV_INT("FMSKF_ISR_FUSED", 1) != 0; }
 
 // the ISR's launches for resolved inputs `t` (frames into `dst`, or none)
 static void isr_launches(fmskf_ctx *h, const TickIn &t, uint8_t *dst) {

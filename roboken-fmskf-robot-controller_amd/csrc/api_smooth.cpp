@@ -62,7 +62,7 @@ void ensure_workspace(fmskf_ctx *h, uint64_t bytes) {
 // FMSKF_SMOOTH_TIME (read per call; for tools/smooth_bench.py): "fwd" / "bwd" lets the timing
 // events bracket that pass alone; anything else, both passes
 int timed_pass() {
-  const char *e = getenv("FMSKF_SMOOTH_TIME");
+  const char *e = env_knob("FMSKF_SMOOTH_TIME");
   return !e ? 0 : !strcmp(e, "fwd") ? 1 : !strcmp(e, "bwd") ? 2 : 0;
 }
 

@@ -122,7 +122,7 @@ __device__ __forceinline__ CanWheel can_wheel(uint32_t fx, uint32_t fy, int16_t 
 // stamps)
 inline bool can_args(const DevState &s, const uint8_t *can_frames, const int16_t *can_stamps, const int8_t dir[4],
                      CanArgs &ca) {
-  if (!s.m_sum_lo || state_nt(s.n * 66) || ((uintptr_t)can_frames & 15) != 0 || ((uintptr_t)can_stamps & 7) != 0)
+  if (!s.m_sum_lo || state_nt(s.n * kMotorStateBytes) || ((uintptr_t)can_frames & 15) != 0 || ((uintptr_t)can_stamps & 7) != 0)
     return false;
   ca = CanArgs{};
   ca.n = s.n;
@@ -151,7 +151,7 @@ inline bool can_args(const DevState &s, const uint8_t *can_frames, const int16_t
 // us, KF6 2^21 299 -> 253-263; isr_tick_can KF6 2^21 306-307 -> 248-250, RS 2^21 255-256 ->
 // 216-217 (the 40 B of frames count: without them RS 2^21 stayed cached); unchanged where
 // everything fits (KF6 / RS 2^20)
-inline bool can_nt(const DevState &s) { return state_nt(s.n * (66 + 40 + est_state_bytes(s))); }
+inline bool can_nt(const DevState &s) { return state_nt(s.n * (kMotorStateBytes + kCanInBytes + est_state_bytes(s))); }
 
 template <bool NT, bool FULL = false>
 struct Can4Lane {

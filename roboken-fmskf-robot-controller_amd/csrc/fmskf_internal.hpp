@@ -8,6 +8,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include "../../include/fmskf.h"
+#include "launch_regime.hpp"
 
 namespace fmskf {
 
@@ -160,7 +161,6 @@ struct Kf6Params {
   // FMSKF_CFG_COMP_POS: the tiled low-part rows (px, py, P00, P10, P11); null = plain fp32
   float *lo;
 };
-constexpr uint32_t kKf6LoRows = 5;
 // The chi-square innovation gate of a KF6 handle (fmskf_set_gate): its configuration and the
 // per-robot gate state, two plain [N] planes read and written by the gated instantiations of the
 // tick kernels alone (kernels_kf6.hip; they take it in an argument struct of their own, kf6_lane.hpp
@@ -390,11 +390,7 @@ template <typename T>
 constexpr uint32_t tile_w() { return sizeof(T) == 8 ? 4096u : 2048u; }  // fp64 (KF12D) / fp32
 inline uint32_t tile_w_elem(uint32_t elem) { return elem == 8 ? 4096u : 2048u; }
 
-// Cache policy of the per-tick state stream.  When the state is several times the 256 MiB
-// Infinity Cache, every state byte is read once and written once per tick from HBM; loading
-// and storing it non-temporal (gfx950 `nt`, buffer aux bit 1) measured 15% faster on the
-// tiled pattern at 2^22 EKF9 robots (tools/membench.hip: 352 -> 299 us), while it is slower
-// when the state fits the Infinity Cache.  FMSKF_STATE_NT=0|1 forces it off or on.
+// The load policy of a streamed state (launch_regime.hpp state_nt): gfx950 `nt`, buffer aux bit 1
 constexpr int kStateNT = 2;
 // Cache policy of the state STORES.  Every state line is written once per tick and not read
 // again in the launch, so a store need not keep it in the XCD's L2: `sc1` (buffer aux bit 4)
@@ -409,37 +405,15 @@ constexpr int kStateNT = 2;
 #endif
 // the store policy that goes with a load policy CP (0: cache-resident state, kStateNT: streamed)
 constexpr int st_pol(int cp) { return cp == kStateNT ? FMSKF_ST_STREAM : FMSKF_ST_CACHED; }
-inline bool state_nt(uint64_t state_bytes) {
-  static const int force = [] {
-    const char *e = getenv("FMSKF_STATE_NT");
-    return e ? atoi(e) : -1;
-  }();
-  if (force >= 0) return force != 0;
-  return state_bytes > (256ull << 20);
-}
 
-// bytes per robot of the handle's estimator state (x, P and the hidden low-part rows): the part
-// of the working set the ingest kernels' cache policies have to leave room for
-inline uint64_t est_state_bytes(const DevState &s) {
-  switch (s.model) {
-    case FMSKF_MODEL_RS: return 56;
-    case FMSKF_MODEL_KF6: return s.xlo ? 128 : 108;
-    case FMSKF_MODEL_EKF9: return s.xlo ? 240 : 220;
-    default: return 90 * 8;  // KF12D
-  }
-}
+// launch_regime.hpp's table for a handle
+inline uint64_t est_state_bytes(const DevState &s) { return est_state_bytes(s.model, s.xlo != nullptr); }
 
-// Occupancy cap for the kernels that stream their state from HBM: dynamic LDS per block limits
-// the resident blocks per CU (160 KiB / bytes), so fewer tile / plane streams compete for the
-// HBM channels.  The environment variable (read once per call site) overrides the byte count.
-#define FMSKF_LDS_CAP(NAME, HBM, DFLT)                              \
-  ([&]() -> unsigned {                                              \
-    static const int v_ = [] {                                      \
-      const char *e_ = getenv(NAME);                                \
-      return e_ ? atoi(e_) : -1;                                    \
-    }();                                                            \
-    return v_ >= 0 ? (unsigned)v_ : ((HBM) ? (unsigned)(DFLT) : 0u); \
-  }())
+// The two 4 GiB window tests, regime boundaries inherited from the planar layout (the tiled arrays
+// need none): there the 21 P planes of a KF6 state (kf6_load_in's array-base input descriptors,
+// Opt::SMALL), and the control state's interpolator planes, had to fit one window
+inline bool kf6_small(const DevState &s) { return s.pitch * 84 < 0xFFFFFFFFull; }
+inline bool ctrl_small(const CtrlDev &c) { return c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull; }
 
 // Run-time bools as compile-time ones: with_bools(f, a, b) calls the generic lambda f with a
 // std::bool_constant per bool, f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a launcher

@@ -282,12 +282,10 @@ int launch_ctrl_set_target(const CtrlDev &c, const float *vel, const float *acl,
 int launch_ctrl_step(const CtrlDev &c, const CtrlPrm &p, const int16_t *rpm, uint32_t rstride,
                      hipStream_t st) {
   if (c.n == 0) return 0;
-  // the window test: a regime boundary inherited from the planar layout (the tiled planes need none)
-  if (c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull && state_nt(ctrl_state_bytes(c)))
-    // 3 blocks per CU (48 KiB dynamic LDS): 2^22 239.4-239.5 -> 235.9-237.0 us
-    k_ctrl_step<kStateNT><<<grid1(c.n), kBlock, FMSKF_LDS_CAP("FMSKF_CTRL_LDS", true, 48u * 1024u), st>>>(c, p, rpm, rstride);
-  else
-    k_ctrl_step<><<<grid1(c.n), kBlock, 0, st>>>(c, p, rpm, rstride);
+  const bool nt = ctrl_small(c) && state_nt(ctrl_state_bytes(c));
+  // 3 blocks per CU (48 KiB dynamic LDS): 2^22 239.4-239.5 -> 235.9-237.0 us
+  const unsigned lds = nt ? FMSKF_LDS_CAP("FMSKF_CTRL_LDS", true, 48u * 1024u) : 0u;
+  with_bools([&](auto NT) { k_ctrl_step<NT() ? kStateNT : 0><<<grid1(c.n), kBlock, lds, st>>>(c, p, rpm, rstride); }, nt);
   return (int)hipGetLastError();
 }
 
@@ -305,25 +303,26 @@ int launch_ctrl_derive(const CtrlDev &c, const CtrlPrm &p, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-template <bool CAN, bool CNT = false, bool PS = false>
+// can: the tick's CAN RX fused in front (null: none); ps: k_isr_rs PS (with CAN only)
 static int isr_rs_l(const DevState &s, const TickIn &in, bool libm, const CtrlDev &c, const CtrlPrm &p,
-                    uint8_t *frames, hipStream_t st, const CanArgs &can) {
+                    uint8_t *frames, hipStream_t st, const CanArgs *can, bool ps) {
   if (c.n == 0) return 0;
   const IsrRsArgs a{s.pitch, (float *)s.x, s.prev_sum, in.yaw_deg, in.rpm, in.angle_sum, in.sum_pitch,
                     in.msum_lo, in.msum_hi, in.sintab, frames, in.imu_words & 1u};
-  // the window test: a regime boundary inherited from the planar layout (the tiled planes need none)
-  const bool nt = c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull && state_nt(ctrl_state_bytes(c) + s.n * 56);
+  const bool nt = ctrl_small(c) && state_nt(ctrl_state_bytes(c) + s.n * kRsStateBytes);
   // 3 blocks per CU (48 KiB dynamic LDS): 2^20 75.7-76.5 -> 73.9 us (two passes)
   const unsigned lds = nt ? FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u) : 0u;
-  with_bools([&](auto LIBM, auto NT) {
-    k_isr_rs<LIBM(), NT() ? kStateNT : 0, CAN, CNT, PS><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, can);
-  }, libm, nt);
+  with_bools([&](auto LIBM, auto NT, auto CAN, auto CNT, auto PS) {
+    if constexpr (CAN() || (!CNT() && !PS()))
+      k_isr_rs<LIBM(), NT() ? kStateNT : 0, CAN(), CNT(), PS()>
+          <<<grid1(c.n), kBlock, lds, st>>>(a, c, p, can ? *can : CanArgs{});
+  }, libm, nt, can != nullptr, can && can_nt(s), can && ps);
   return (int)hipGetLastError();
 }
 
 int launch_isr_rs(const DevState &s, const TickIn &in, bool libm, const CtrlDev &c,
                   const CtrlPrm &p, uint8_t *frames, hipStream_t st) {
-  return isr_rs_l<false>(s, in, libm, c, p, frames, st, CanArgs{});
+  return isr_rs_l(s, in, libm, c, p, frames, st, nullptr, false);
 }
 
 // The fused KF6 ISR where it applies: one tick of the default single-tick form (state in one
@@ -331,53 +330,25 @@ int launch_isr_rs(const DevState &s, const TickIn &in, bool libm, const CtrlDev 
 // per lane), the control planes in one window.  Returns hipErrorNotSupported otherwise (the
 // caller then runs the three kernels).  Past the Infinity Cache (KF6 state + control state
 // > 256 MiB) the control planes are non-temporal, as in k_isr_rs.
-template <bool LIBM, bool VALID, bool REC, bool COMP>
-static int isr_kf6_v(const KfArgs<MdKF6, Kf6Params> &a, const CtrlDev &c, const CtrlPrm &p, uint8_t *frames,
-                     bool nt, hipStream_t st, const CanArgs *can) {
-  using O = Opt<LIBM, true, true, true, VALID, REC, false, false, COMP>;
-  const unsigned lds = nt ? FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u) : 0u;
-  if constexpr (!REC) {  // with CAN the rpm comes from the frames, so the inputs are planes
-    if (can && can_nt_flag(*can)) {
-      if (nt) k_isr_kf6<O, kStateNT, true, true><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, frames, *can);
-      else k_isr_kf6<O, 0, true, true><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, frames, *can);
-      return (int)hipGetLastError();
-    }
-    if (can) {
-      if (nt) k_isr_kf6<O, kStateNT, true><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, frames, *can);
-      else k_isr_kf6<O, 0, true><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, frames, *can);
-      return (int)hipGetLastError();
-    }
-  }
-  if (can) return (int)hipErrorNotSupported;
-  if (nt) k_isr_kf6<O, kStateNT><<<grid1(c.n), kBlock, lds, st>>>(a, c, p, frames, CanArgs{});
-  else k_isr_kf6<O, 0><<<grid1(c.n), kBlock, 0, st>>>(a, c, p, frames, CanArgs{});
-  return (int)hipGetLastError();
-}
-
-template <bool COMP>
-static int isr_kf6_c(const KfArgs<MdKF6, Kf6Params> &a, const CtrlDev &c, const CtrlPrm &p, uint8_t *frames, bool nt,
-                     hipStream_t st, bool libm, bool valid, bool rec, const CanArgs *can) {
-  return with_bools([&](auto LIBM, auto VALID, auto REC) {
-    return isr_kf6_v<LIBM(), VALID(), REC(), COMP>(a, c, p, frames, nt, st, can);
-  }, libm, valid, rec);
-}
-
 static int isr_kf6_l(const DevState &s, const TickIn &in, const Kf6Params &kp, bool libm, const CtrlDev &c,
                      const CtrlPrm &p, uint8_t *frames, hipStream_t st, const CanArgs *can) {
   if (c.n == 0) return 0;
-  // both window tests: regime boundaries inherited from the planar layout (the tiled arrays need none)
-  const bool small_state = s.pitch * 84 < 0xFFFFFFFFull;
-  const bool small_ctrl = c.pitch * 4 * 3 * kAxF < 0xFFFFFFFFull;
   // the tick kernel alone streams its state non-temporal past the cache: keep that regime on
   // the three-kernel path (its own occupancy caps)
-  // KF6 state bytes per robot (FMSKF_CFG_COMP_POS: + the position low parts)
-  const uint64_t sb = kp.lo ? 128 : 108;
-  if (!small_state || !small_ctrl || state_nt(s.n * sb)) return (int)hipErrorNotSupported;
+  const uint64_t sb = kf6_state_bytes(kp.lo != nullptr);
+  if (!kf6_small(s) || !ctrl_small(c) || state_nt(s.n * sb)) return (int)hipErrorNotSupported;
+  // with CAN the rpm comes from the frames, so the inputs are planes
+  if (can && in.rec) return (int)hipErrorNotSupported;
   const KfArgs<MdKF6, Kf6Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, kp};
   const bool nt = state_nt(ctrl_state_bytes(c) + s.n * sb);
-  const bool valid = in.valid != nullptr, rec = in.rec != nullptr;
-  return kp.lo ? isr_kf6_c<true>(a, c, p, frames, nt, st, libm, valid, rec, can)
-               : isr_kf6_c<false>(a, c, p, frames, nt, st, libm, valid, rec, can);
+  const unsigned lds = nt ? FMSKF_LDS_CAP("FMSKF_ISR_LDS", true, 48u * 1024u) : 0u;
+  with_bools([&](auto LIBM, auto VALID, auto REC, auto COMP, auto NT, auto CAN, auto CNT) {
+    using O = Opt<LIBM(), true, true, true, VALID(), REC(), false, false, COMP()>;
+    if constexpr (CAN() ? !REC() : !CNT())
+      k_isr_kf6<O, NT() ? kStateNT : 0, CAN(), CNT()>
+          <<<grid1(c.n), kBlock, lds, st>>>(a, c, p, frames, can ? *can : CanArgs{});
+  }, libm, in.valid != nullptr, in.rec != nullptr, kp.lo != nullptr, nt, can != nullptr, can && can_nt_flag(*can));
+  return (int)hipGetLastError();
 }
 
 int launch_isr_kf6(const DevState &s, const TickIn &in, const Kf6Params &kp, bool libm, const CtrlDev &c,
@@ -406,12 +377,7 @@ int launch_isr_rs_can(const DevState &s, const TickIn &in, bool libm, const Ctrl
                       bool prev_in_sums, hipStream_t st) {
   CanArgs ca;
   if (!can_args(s, can_frames, can_stamps, dir, ca)) return (int)hipErrorNotSupported;
-  if (prev_in_sums) {
-    if (can_nt(s)) return isr_rs_l<true, true, true>(s, in, libm, c, p, frames, st, ca);
-    return isr_rs_l<true, false, true>(s, in, libm, c, p, frames, st, ca);
-  }
-  if (can_nt(s)) return isr_rs_l<true, true>(s, in, libm, c, p, frames, st, ca);
-  return isr_rs_l<true>(s, in, libm, c, p, frames, st, ca);
+  return isr_rs_l(s, in, libm, c, p, frames, st, &ca, prev_in_sums);
 }
 
 int launch_can_tx(const CtrlDev &c, uint8_t *frames, hipStream_t st) {

@@ -554,88 +554,52 @@ __global__ __launch_bounds__(kBlock) void k_kf12s(KfArgs<MdKF12D, Kf12dParams> a
 // epilogue (and the carried fold blocks past the tick blocks when in.fold_blocks is set);
 // returns the tick grid (= the number of block records)
 template <bool LIBM, bool SEQ, bool COMP>
-static int launch_ekf9_ens(KfArgs<MdEKF9, Ekf9Params> a, const DevState &s, bool nt, hipStream_t st) {
+static int launch_ekf9_ens(KfArgs<MdEKF9, Ekf9Params> a, hipStream_t st) {
   const unsigned carry = a.in.fold_blocks ? (unsigned)EnsRec<9>::LEN : 0u;
-  if (!LIBM && s.n * (COMP ? 240 : 220) <= (256ull << 20)) {
-    const uint32_t ntiles = (uint32_t)((s.n + kBlock - 1) / kBlock);
-    const unsigned g2 = (ntiles + 1) / 2;
-    a.in.ens_grid = g2;
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_EKF9P_LDS", true, 64u * 1024u);
-    if (nt) launch_signal(k_ekf9p<false, SEQ, kStateNT, true, COMP>, dim3(g2 + carry), lds, st, a.in.ens_done, a);
-    else launch_signal(k_ekf9p<false, SEQ, 0, true, COMP>, dim3(g2 + carry), lds, st, a.in.ens_done, a);
-    return (int)g2;
-  }
-  // past the Infinity Cache the record epilogue (fp64 sums and their cross-lane reduction)
-  // wants one more block per CU than the plain tick: 2^22, kbench, two passes: 331-335 us at
-  // 64 KiB (2 blocks per CU), 307-308 at 32 KiB (3), 316 uncapped
-  const unsigned g = grid_for(s.n).x;
+  const LaunchRegime r = ekf9_ens_regime(a.n, COMP, LIBM);
+  const unsigned ntiles = grid_for(a.n).x, g = r.two ? (ntiles + 1) / 2 : ntiles;
   a.in.ens_grid = g;
-  const unsigned lds = LIBM ? 0u : FMSKF_LDS_CAP("FMSKF_EKF9E_LDS", nt, 32u * 1024u);
-  if (nt) launch_signal(k_ekf9t<LIBM, true, true, SEQ, kStateNT, true, COMP>, dim3(g + carry), lds, st, a.in.ens_done, a);
-  else launch_signal(k_ekf9t<LIBM, true, true, SEQ, 0, true, COMP>, dim3(g + carry), lds, st, a.in.ens_done, a);
+  with_bools([&](auto TWO, auto NT) {
+    constexpr int CP = NT() ? kStateNT : 0;
+    if constexpr (TWO() && !LIBM)
+      launch_signal(k_ekf9p<false, SEQ, CP, true, COMP>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
+    else if constexpr (!TWO())
+      launch_signal(k_ekf9t<LIBM, true, true, SEQ, CP, true, COMP>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
+  }, r.two, r.nt);
   return (int)g;
 }
 
-// The launch regime of a single full tick, shared by the plain and the row-gated handles: two
-// robots per lane (k_ekf9p) while the state -- sb bytes per robot, with the gate word where there
-// is one -- fits the 256 MiB Infinity Cache, else one per lane (k_ekf9t); FMSKF_EKF9_VARIANT
-// (read once) forces one of them, 2 = k_ekf9p, 4 = k_ekf9t (the tests' cross-check at small N).
-// Measured (kbench, one box, two passes): 2^20 k_ekf9t 74.8-74.9 us, k_ekf9p 71.2-71.9; 2^22
-// (HBM) k_ekf9t 336-338, k_ekf9p 339.  A raised-priority load phase (s_setprio 3 while issuing
-// the loads) measured 71.2-73.9 at 2^20 and 342-343 at 2^22 and was removed.
-struct Ekf9Regime {
-  bool two;
-  unsigned lds;
-};
-static Ekf9Regime ekf9_regime(uint64_t n, uint64_t sb, bool libm, bool nt) {
-  static const int var = [] {
-    const char *e = getenv("FMSKF_EKF9_VARIANT");
-    return e ? atoi(e) : 0;
-  }();
-  const int v = var == 2 || var == 4 ? var : (n * sb <= (256ull << 20) ? 2 : 4);
-  // 64 KiB of dynamic LDS (2 blocks per CU): 2^20 71.2 -> 70.5-70.7 us (two passes)
-  if (!libm && v == 2) return {true, FMSKF_LDS_CAP("FMSKF_EKF9P_LDS", true, 64u * 1024u)};
-  if (libm) return {false, 0u};
-  // Past the Infinity Cache (non-temporal state) the occupancy is capped at 2 blocks per CU
-  // with 64 KiB of dynamic LDS: fewer concurrent tile streams per HBM channel.  2^22:
-  // 334.3-338.7 us uncapped, 332 at 32 KiB, 329.7-331.0 at 48 KiB, 326.8-330.9 at 64 KiB,
-  // 382-383 at 80 KiB (kbench, two boxes, two passes each); the same-bytes tiled pattern
-  // (membench) 299 us.  FMSKF_EKF9_LDS overrides the byte count.
-  return {false, FMSKF_LDS_CAP("FMSKF_EKF9_LDS", nt, 64u * 1024u)};
-}
-
 // A: Ekf9Args, or RowGateArgs for a row-gated handle (update launches with a diagonal R only:
-// launch_ekf9_rowgate); sb: state (+ gate word) bytes per robot, nt: whether they stream
+// launch_ekf9_rowgate).  The single full tick goes by ekf9_regime (launch_regime.hpp); every other
+// form is one robot per lane, cached and uncapped
 template <bool LIBM, bool SEQ, bool COMP, class A>
-static void launch_ekf9_l(const A &aa, uint64_t sb, bool upd, bool pred, bool nt, hipStream_t st) {
+static void launch_ekf9_l(const A &aa, bool upd, bool pred, hipStream_t st) {
   constexpr bool GATED = std::is_same<A, RowGateArgs>::value;
   const Ekf9Args &a = kf_args(aa);
   const dim3 g = grid_for(a.n);
-  if (a.in.n_ticks != 1) {
-    if (upd && pred) k_ekf9<LIBM, true, true, SEQ, COMP, A><<<g, kBlock, 0, st>>>(aa);
-    else if constexpr (!GATED) {
-      if (upd) k_ekf9<LIBM, true, false, SEQ, COMP><<<g, kBlock, 0, st>>>(aa);
-      else k_ekf9<LIBM, false, true, false, COMP><<<g, kBlock, 0, st>>>(aa);
-    }
-  } else if (upd && pred) {
-    const Ekf9Regime r = ekf9_regime(a.n, sb, LIBM, nt);
-    if constexpr (!LIBM) {
-      if (r.two) {
-        const uint32_t ntiles = (uint32_t)((a.n + kBlock - 1) / kBlock);
-        const dim3 g2((ntiles + 1) / 2);
-        if (nt) k_ekf9p<false, SEQ, kStateNT, false, COMP, A><<<g2, kBlock, r.lds, st>>>(aa);
-        else k_ekf9p<false, SEQ, 0, false, COMP, A><<<g2, kBlock, r.lds, st>>>(aa);
-        return;
-      }
-    }
-    if (nt) k_ekf9t<LIBM, true, true, SEQ, kStateNT, false, COMP, A><<<g, kBlock, r.lds, st>>>(aa);
-    else k_ekf9t<LIBM, true, true, SEQ, 0, false, COMP, A><<<g, kBlock, r.lds, st>>>(aa);
-  } else if (upd) {
-    k_ekf9t<LIBM, true, false, SEQ, 0, false, COMP, A><<<g, kBlock, 0, st>>>(aa);
-  } else if constexpr (!GATED) {
-    // predict-only launches run no update: one (SEQ = false) instantiation serves both
-    k_ekf9t<LIBM, false, true, false, 0, false, COMP><<<g, kBlock, 0, st>>>(aa);
+  const bool many = a.in.n_ticks != 1;
+  if (!many && upd && pred) {
+    const LaunchRegime r = ekf9_regime(a.n, COMP, GATED, LIBM);
+    with_bools([&](auto TWO, auto NT) {
+      constexpr int CP = NT() ? kStateNT : 0;
+      if constexpr (TWO() && !LIBM)
+        k_ekf9p<false, SEQ, CP, false, COMP, A><<<dim3((g.x + 1) / 2), kBlock, r.lds, st>>>(aa);
+      else if constexpr (!TWO())
+        k_ekf9t<LIBM, true, true, SEQ, CP, false, COMP, A><<<g, kBlock, r.lds, st>>>(aa);
+    }, r.two, r.nt);
+    return;
   }
+  with_bools([&](auto MANY, auto UPD, auto PRED) {
+    constexpr bool FULL = UPD() && PRED();
+    // predict-only launches run no update: one (SEQ = false) instantiation serves both
+    constexpr bool S = UPD() && SEQ;
+    // the row-gated handle has the full tick_many and the single correct alone
+    constexpr bool HAVE = MANY() ? FULL || (!GATED && (UPD() || PRED())) : !FULL && (UPD() || (!GATED && PRED()));
+    if constexpr (HAVE) {
+      if constexpr (MANY()) k_ekf9<LIBM, UPD(), PRED(), S, COMP, A><<<g, kBlock, 0, st>>>(aa);
+      else k_ekf9t<LIBM, UPD(), PRED(), S, 0, false, COMP, A><<<g, kBlock, 0, st>>>(aa);
+    }
+  }, many, upd, pred || !upd);
 }
 
 int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool libm, bool upd,
@@ -644,20 +608,19 @@ int launch_ekf9(const DevState &s, const TickIn &in, const Ekf9Params &p, bool l
   a.prm.thlo = s.thlo;
   a.prm.clo = s.xlo;  // FMSKF_CFG_COMP_POS
   if (!s.thlo) return (int)hipErrorInvalidValue;
-  const bool nt = state_nt(s.n * (s.xlo ? 60 : 55) * 4);
   if ((in.ens_blocks && (!ens_nb || !upd || !pred || in.n_ticks != 1)) || (in.fold_blocks && !in.ens_blocks))
     return (int)hipErrorInvalidValue;
   // canonical update order (oracle orc_ekf9_tick): sequential scalar updates when R is
   // diagonal (SEQ), the joint LDL^T update otherwise
   with_bools([&](auto LIBM, auto SEQ, auto COMP) {
-    if (in.ens_blocks) *ens_nb = launch_ekf9_ens<LIBM(), SEQ(), COMP()>(a, s, nt, st);
-    else launch_ekf9_l<LIBM(), SEQ(), COMP()>(a, COMP() ? 240 : 220, upd, pred, nt, st);
+    if (in.ens_blocks) *ens_nb = launch_ekf9_ens<LIBM(), SEQ(), COMP()>(a, st);
+    else launch_ekf9_l<LIBM(), SEQ(), COMP()>(a, upd, pred, st);
   }, libm, ekf9_r_diagonal(p.r), s.xlo != nullptr);
   return (int)hipGetLastError();
 }
 
 // The row-gated handle (fmskf_set_row_gate): the same kernels on RowGateArgs through the same
-// regimes, 228 B of state + gate word per robot.  No fused ensemble record, no ISR form, no
+// regimes, with the gate word in the bytes per robot.  No fused ensemble record, no ISR form, no
 // compensated positions: the callers take the stand-alone record / the three-kernel ISR / refuse
 // the gate.
 int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p, const RowGateDev &g,
@@ -669,9 +632,7 @@ int launch_ekf9_rowgate(const DevState &s, const TickIn &in, const Ekf9Params &p
   RowGateArgs ga{{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p}, g};
   ga.k.prm.thlo = s.thlo;
   ga.k.prm.clo = nullptr;
-  const bool nt = state_nt(s.n * 228);
-  if (libm) launch_ekf9_l<true, true, false>(ga, 228, true, pred, nt, st);
-  else launch_ekf9_l<false, true, false>(ga, 228, true, pred, nt, st);
+  with_bools([&](auto LIBM) { launch_ekf9_l<LIBM(), true, false>(ga, true, pred, st); }, libm);
   return (int)hipGetLastError();
 }
 
@@ -679,10 +640,8 @@ template <bool CAN>
 static int isr_ekf9_l(const DevState &s, const TickIn &in, const Ekf9Params &prm, bool libm, const CtrlDev &c,
                       const CtrlPrm &p, const int16_t *rpm, uint8_t *frames, hipStream_t st, const CanArgs &can) {
   if (c.n == 0) return 0;
-  const uint64_t sb = s.xlo ? 240 : 220;  // state bytes per robot (+ the compensation rows)
-  // the window test on the control planes: a regime boundary inherited from the planar layout
-  if (!s.thlo || in.n_ticks != 1 || !in.raw || (!CAN && !rpm) || state_nt(s.n * sb) ||
-      c.pitch * 4 * 3 * kAxF >= 0xFFFFFFFFull)
+  const uint64_t sb = ekf9_state_bytes(s.xlo != nullptr);
+  if (!s.thlo || in.n_ticks != 1 || !in.raw || (!CAN && !rpm) || state_nt(s.n * sb) || !ctrl_small(c))
     return (int)hipErrorNotSupported;
   KfArgs<MdEKF9, Ekf9Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, prm};
   a.prm.thlo = s.thlo;
@@ -722,7 +681,8 @@ int launch_kf12d(const DevState &s, const TickIn &in, const Kf12dParams &p, bool
                  hipStream_t st, int *ens_nb) {
   KfArgs<MdKF12D, Kf12dParams> a{s.n, s.pitch, (double *)s.x, (double *)s.P, in, s.counters, p};
   const dim3 g = grid_for(s.n);
-  const bool nt = state_nt(s.n * 90 * 8);
+  const LaunchRegime r = kf12d_regime(s.n);
+  const bool nt = r.nt;
   // SP (the default R and Q: sparse C^-1 and Q, checked on the host) implies BLK
   const bool sp = p.sparse != 0, blk = kf12d_sequential(p.r);
   if (in.fold_blocks && !in.ens_blocks) return (int)hipErrorInvalidValue;
@@ -741,10 +701,9 @@ int launch_kf12d(const DevState &s, const TickIn &in, const Kf12dParams &p, bool
   }
   if (p.decor) {
     if (upd && pred) {
-      const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF12D_LDS", nt, 0u);
       with_bools([&](auto BLK, auto SP, auto NT) {
         if constexpr (BLK() || !SP())
-          k_kf12s<BLK(), true, true, NT() ? kStateNT : 0, false, SP()><<<g, kBlock, lds, st>>>(a);
+          k_kf12s<BLK(), true, true, NT() ? kStateNT : 0, false, SP()><<<g, kBlock, r.lds, st>>>(a);
       }, sp || blk, sp, nt);
     } else if (upd) {
       with_bools([&](auto BLK) { k_kf12s<BLK(), true, false><<<g, kBlock, 0, st>>>(a); }, blk);

@@ -6,7 +6,7 @@
 // VD_vehicle_controller.cpp:21-51) + LDL^T-form update + F P F^T + Q predict, one read and
 // one write of every state byte: 232 algorithmic bytes per instance-tick (the write of the
 // masked cross-covariance planes, kf6_lane.hpp, is issued only where a lane's value changed).
-// The mask belongs to the launch regime (kf6_wide below): the two-per-lane full tick takes all
+// The mask belongs to the launch regime (kf6_wide, launch_regime.hpp): the two-per-lane full tick takes all
 // eight cross planes (Opt WIDE) while state + inputs fill at most half the Infinity Cache, every
 // other launch their position half (kKf6SkipMask); the kernels without WIDE are the code they
 // were before the split (profiles/kf6_half_cache_bodies.json).
@@ -31,7 +31,7 @@
 //
 // The chi-square innovation gate (fmskf_set_gate) is an instantiation of the same kernels on
 // GateArgs (kf6_lane.hpp): one more lane struct loaded with the state and stored with it, the
-// gated update inside kf6_tick1, the launch regimes of the plain handle (kf6_regime).
+// gated update inside kf6_tick1, the launch regimes of the plain handle (kf6_regime, launch_regime.hpp).
 #include "ens_device.hpp"
 #include "kf6_lane.hpp"
 
@@ -189,75 +189,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   if constexpr (O::ENS) ens_epilogue<6, R>(a.in, xs, lv, bid);
 }
 
-// Variant (FMSKF_KF6_VARIANT, read once) for single-tick launches; default 0:
-//   0: k_kf6p with 2 robots per lane while 124 B x N fits the Infinity Cache, else 15
-//   15: one instance per lane, grid = N/256, straight-line single-tick kernel (k_kf6t)
-//   12: k_kf6p with 2 robots per lane at any N
-// (the tests force 12 / 15 at small N to check both kernels).  Measured and removed: 3 or 4
-// robots per lane (38.0 us at 2^20 against 37.4-38.6 for 2), the single tick through the
-// tick-loop kernel, and persistent double-buffered kernels at 2-8 blocks per CU (5-20% slower).
-static int kf6_variant() {
-  static int v = [] {
-    const char *e = getenv("FMSKF_KF6_VARIANT");
-    const int x = e ? atoi(e) : 0;
-    return x == 12 || x == 15 ? x : 0;
-  }();
-  return v;
-}
-
-// The launch regime of a single tick / predict / correct, shared by the plain and the gated
-// handles: two robots per lane or one, whether the state streams past the caches (nt), the
-// dynamic-LDS occupancy cap.  sb: state bytes per robot, with the gate word and NIS where there
-// are any.  two_nt: the caller has a streamed two-per-lane kernel (the gated family has none:
-// its streamed state always goes one robot per lane)
-struct Kf6Regime {
-  bool two, nt;
-  unsigned lds;
-};
-static Kf6Regime kf6_regime(uint64_t n, uint64_t sb, bool rec, bool two_nt) {
-  const int v = kf6_variant();
-  const uint64_t rb = sb + 16;  // with one tick's 16-byte inputs
-  const bool nt = state_nt(n * sb);
-  if ((two_nt || !nt) && (v == 12 || (v == 0 && n * rb <= (256ull << 20)))) {
-    // state + one tick's inputs resident in the 256 MiB Infinity Cache: two robots per lane,
-    // both robots' inputs loaded up front, one wave round (2^20: 39.7 -> 37.4-38.1 us,
-    // 2^21: 75.9 -> 71.5; at 2^24, HBM-bound, it is 3% slower than one robot per lane)
-    if (v == 12) return {true, nt, 0u};
-    // 32 KiB of dynamic LDS: at most 5 blocks per CU.  kbench, records, two passes: 2^20
-    // 38.2-38.5 -> 37.2-37.3 us (24 KiB 37.6-37.7, 40 KiB 37.4-37.5); 2^21 71.6-71.8 -> 70.5-70.9.
-    // Records fed while state + inputs fill at most half the cache (2^20 robots): 48 KiB, 3
-    // blocks per CU (round 3, kbench, three alternating passes on one box: 32 KiB 36.99-37.14 us,
-    // 48 KiB 36.67-36.93, 64 KiB 36.61-36.97, 80 KiB 44.0, uncapped 38.0).  Plane inputs and
-    // 2^21 records stay at 32 KiB (48 KiB: 2^20 planes 37.49 -> 37.72-38.07, 2^21 records
-    // 68.3-68.4 -> 69.0, 2^21 planes 69.5-69.7 -> 71.2-71.4)
-    const bool rec_half = rec && n * rb <= (128ull << 20);
-    return {true, nt, FMSKF_LDS_CAP("FMSKF_KF6P_LDS", true, rec_half ? 48u * 1024u : 32u * 1024u)};
-  }
-  // past the Infinity Cache: at most 3 blocks per CU (48 KiB of dynamic LDS).  2^24, records,
-  // kbench, one box, two passes: 691-704 us uncapped, 671-684 at 32 KiB, 627-641 at 48 KiB,
-  // 626-639 at 64 KiB, 809-826 at 80 KiB (two blocks of 4 waves per CU are too few)
-  return {false, nt, FMSKF_LDS_CAP("FMSKF_KF6_LDS", nt, 48u * 1024u)};
-}
-
-// Which write-back mask a two-per-lane full tick (ungated, not COMP) takes: the eight cross planes
-// (Opt WIDE) while state + one tick's inputs fill at most half the Infinity Cache, the position
-// half past that.  The split is NOT the hardware's: the wide mask measured faster at 2^21 and 2^24
-// too (profiles/kf6_skip_store_ab.json).  It is the roofline check's: tests/test_gpu_bench_line.py
-// prices every KF6 row at the algorithmic 232 B per robot-tick and wants the row below that model's
-// bandwidth ceiling, and the project holds every KF6-fed row of a --full line to frac <= 0.97.
-// With the wide mask the 2^21 shard row read 0.983; the headline regime has room (0.913;
-// profiles/kf6_half_cache_ab.json).
-// FMSKF_KF6_SKIP_WIDE (read once): 0 narrow in every regime, 1 wide in every two-per-lane full
-// tick, unset by the regime.  sb: state bytes per robot
-static bool kf6_wide(uint64_t n, uint64_t sb) {
-  static const int force = [] {
-    const char *e = getenv("FMSKF_KF6_SKIP_WIDE");
-    return e ? atoi(e) : -1;
-  }();
-  if (force == 0 || force == 1) return force == 1;
-  return n * (sb + 16) <= (128ull << 20);
-}
-
 // A FOLD instantiation on the tick grid g: the LEN fold blocks of the pending ensemble event
 // ahead of the tick blocks, as launch_ens_o launches a record tick that carries one
 template <class A>
@@ -289,7 +220,7 @@ static void launch_o(const A &aa, hipStream_t st) {
       k_kf6<4, O, A><<<grid_for(a.n), kBlock, 0, st>>>(aa);
       return;
     }
-    const Kf6Regime r = kf6_regime(a.n, O::COMP ? 128 : GATED ? 116 : 108, a.in.rec != nullptr, !GATED);
+    const LaunchRegime r = kf6_regime(a.n, O::COMP, GATED, a.in.rec != nullptr);
     // the streamed (non-temporal) kernels exist for the full tick only; in a two-per-lane launch
     // only when forced, since that regime's state fits the cache
     constexpr bool NT = O::UPD && O::PRED;
@@ -298,7 +229,7 @@ static void launch_o(const A &aa, hipStream_t st) {
       if constexpr (NT && !GATED) {
         // the ungated full tick: streamed, with the wide mask (kf6_wide; never COMP, whose
         // kernels stay as they were) and / or carrying a pending ensemble fold (run_tick)
-        const bool wide = !O::COMP && kf6_wide(a.n, 108), fold = a.in.fold_blocks != nullptr;
+        const bool wide = !O::COMP && kf6_wide(a.n), fold = a.in.fold_blocks != nullptr;
         if (r.nt || wide || fold) {
           with_bools([&](auto N, auto W, auto F) {
             using ON = std::conditional_t<N(), WithNT<O>, O>;
@@ -314,18 +245,11 @@ static void launch_o(const A &aa, hipStream_t st) {
     }
     if constexpr (NT && !GATED) {
       if (a.in.fold_blocks) {  // one robot per lane, carrying a pending ensemble fold
-        if (r.nt) launch_one<WithFold<WithNT<O>>>(aa, r.lds, st);
-        else launch_one<WithFold<O>>(aa, r.lds, st);
+        with_bools([&](auto N) { launch_one<WithFold<std::conditional_t<N(), WithNT<O>, O>>>(aa, r.lds, st); }, r.nt);
         return;
       }
     }
-    if constexpr (NT) {
-      if (r.nt) {
-        launch_one<WithNT<O>>(aa, r.lds, st);
-        return;
-      }
-    }
-    launch_one<O>(aa, r.lds, st);
+    with_bools([&](auto N) { launch_one<std::conditional_t<N() && NT, WithNT<O>, O>>(aa, r.lds, st); }, r.nt);
   }
 }
 
@@ -338,31 +262,19 @@ template <class O>
 static int launch_ens_o(KfArgs<MdKF6, Kf6Params> a, hipStream_t st) {
   using E = WithEns<O>;
   const unsigned carry = a.in.fold_blocks ? (unsigned)EnsRec<6>::LEN : 0u;
-  constexpr uint64_t SB = O::COMP ? 128 : 108, RB = SB + 16;
-  if (a.n * RB <= (256ull << 20)) {
-    const unsigned g = (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock));
-    a.in.ens_grid = g;
-    // 32 KiB in every regime, not the plain record-fed tick's 48 KiB at 2^20 (kf6_regime): the
-    // record epilogue wants the fifth block per CU.  kbench ens_async, records, 2^20, three
-    // alternating passes on one box: K = 1 36.18-36.37 us per tick at 32 KiB against 38.08-38.20 at
-    // 48 KiB; the bench's K = 16 region shape (20 ticks, one event) 34.29-34.47 against 34.47-34.49
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF6PE_LDS", true, 32u * 1024u);
-    // the write-back mask of the plain tick of the same regime (kf6_wide)
-    with_bools([&](auto N, auto W) {
-      using EN = std::conditional_t<N(), WithNT<E>, E>;
-      using EW = std::conditional_t<W() && !O::COMP, WithWide<EN>, EN>;
-      launch_signal(k_kf6p<4, 2, EW>, dim3(g + carry), lds, st, a.in.ens_done, a);
-    }, state_nt(a.n * SB), !O::COMP && kf6_wide(a.n, SB));
-    return (int)g;
-  }
-  // past the Infinity Cache the record epilogue (fp64 sums and their cross-lane reduction)
-  // wants a smaller cap than the plain tick: 2^24, kbench, two passes: 738 us at 48 KiB,
-  // 665-670 at 32 KiB, 680-689 at 24 KiB, 722-724 uncapped (the plain tick: 619-628)
-  const unsigned g = grid_for(a.n).x;
+  const LaunchRegime r = kf6_ens_regime(a.n, O::COMP);
+  const unsigned g = r.two ? (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock)) : grid_for(a.n).x;
   a.in.ens_grid = g;
-  const unsigned lds = FMSKF_LDS_CAP("FMSKF_KF6E_LDS", state_nt(a.n * SB), 32u * 1024u);
-  if (state_nt(a.n * SB)) launch_signal(k_kf6t<4, WithNT<E>>, dim3(g + carry), lds, st, a.in.ens_done, a);
-  else launch_signal(k_kf6t<4, E>, dim3(g + carry), lds, st, a.in.ens_done, a);
+  // two per lane: the write-back mask of the plain tick of the same regime (kf6_wide)
+  with_bools([&](auto TWO, auto N, auto W) {
+    using EN = std::conditional_t<N(), WithNT<E>, E>;
+    if constexpr (TWO()) {
+      using EW = std::conditional_t<W() && !O::COMP, WithWide<EN>, EN>;
+      launch_signal(k_kf6p<4, 2, EW>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
+    } else if constexpr (!W()) {
+      launch_signal(k_kf6t<4, EN>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
+    }
+  }, r.two, r.nt, r.two && !O::COMP && kf6_wide(a.n));
   return (int)g;
 }
 
@@ -380,9 +292,7 @@ static void launch_sel(const KfArgs<MdKF6, Kf6Params> &a, hipStream_t st, int *e
 int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, bool upd,
                bool pred, hipStream_t st, int *ens_nb) {
   KfArgs<MdKF6, Kf6Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p};
-  // Opt::SMALL (kf6_load_in's array-base input descriptors); the bound is a regime boundary
-  // inherited from the planar layout, whose 21 P planes had to fit one 4 GiB window
-  const bool small = s.pitch * 84 < 0xFFFFFFFFull;
+  const bool small = kf6_small(s);  // Opt::SMALL
   const bool valid = upd && in.valid != nullptr, rec = upd && in.rec != nullptr;
   const bool comp = p.lo != nullptr;  // FMSKF_CFG_COMP_POS
   int *nb = in.ens_blocks && upd && pred && in.n_ticks == 1 ? ens_nb : nullptr;

@@ -197,53 +197,23 @@ int launch_rs(const DevState &s, const TickIn &in, bool libm, bool correct, bool
               hipStream_t st) {
   RsArgs a{s.n, s.pitch, (float *)s.x, s.prev_sum, in};
   const dim3 g((unsigned)((s.n + kBlock - 1) / kBlock));
-  static const bool two = [] {  // A/B switch (FMSKF_RS_TWO=0: one robot per lane)
-    const char *e = getenv("FMSKF_RS_TWO");
-    return !e || atoi(e) != 0;
-  }();
-  if (two && correct && predict && in.n_ticks == 1) {
+  const LaunchRegime r = rs_regime(s.n);
+  if (r.two && correct && predict && in.n_ticks == 1) {
     const dim3 g2((unsigned)((s.n + 2 * kBlock - 1) / (2 * kBlock)));
-    // past the Infinity Cache: 2 blocks per CU (64 KiB of dynamic LDS).  2^24, kbench, two
-    // passes: 436.7-448.2 us uncapped, 429-430 at 48 KiB, 418.5-424.5 at 64 KiB
-    const unsigned lds = FMSKF_LDS_CAP("FMSKF_RS_LDS", state_nt(s.n * 124), 64u * 1024u);
     // FMSKF_RS_VARIANT=0: one clamped descriptor per plane (A/B); the soffset form needs every
     // plane array within 4 GiB of its chunk base
-    static const int var = [] {
-      const char *e = getenv("FMSKF_RS_VARIANT");
-      return e ? atoi(e) : 1;
-    }();
-    const bool so = var != 0 && 6 * s.pitch * 4 <= 0xFFFFFFFFull && 4 * in.sum_pitch * 8 <= 0xFFFFFFFFull;
-    const bool ms = in.msum_lo != nullptr;
-    auto go = [&](auto cp, auto so_, auto ms_) {
-      constexpr int C = decltype(cp)::value;
-      constexpr bool S = decltype(so_)::value, M = decltype(ms_)::value;
-      if (libm) k_rs2<true, C, S, M><<<g2, kBlock, lds, st>>>(a);
-      else k_rs2<false, C, S, M><<<g2, kBlock, lds, st>>>(a);
-    };
-    using T = std::true_type;
-    using F = std::false_type;
-    using NT = std::integral_constant<int, kStateNT>;
-    using C0 = std::integral_constant<int, 0>;
-    if (state_nt(s.n * 124)) {
-      if (ms) go(NT{}, T{}, T{});
-      else if (so) go(NT{}, T{}, F{});
-      else go(NT{}, F{}, F{});
-    } else {
-      if (ms) go(C0{}, T{}, T{});
-      else if (so) go(C0{}, T{}, F{});
-      else go(C0{}, F{}, F{});
-    }
+    const bool so = FMSKF_ENV_INT("FMSKF_RS_VARIANT", 1) != 0 && 6 * s.pitch * 4 <= 0xFFFFFFFFull &&
+                    4 * in.sum_pitch * 8 <= 0xFFFFFFFFull;
+    const bool ms = in.msum_lo != nullptr;  // the motor state's sums: always the soffset form
+    with_bools([&](auto LIBM, auto NT, auto SO, auto MS) {
+      if constexpr (SO() || !MS()) k_rs2<LIBM(), NT() ? kStateNT : 0, SO(), MS()><<<g2, kBlock, r.lds, st>>>(a);
+    }, libm, r.nt, so || ms, ms);
     return (int)hipGetLastError();
   }
-  if (libm) {
-    if (correct && predict) k_rs<true, true, true><<<g, kBlock, 0, st>>>(a);
-    else if (correct) k_rs<true, true, false><<<g, kBlock, 0, st>>>(a);
-    else k_rs<true, false, true><<<g, kBlock, 0, st>>>(a);
-  } else {
-    if (correct && predict) k_rs<false, true, true><<<g, kBlock, 0, st>>>(a);
-    else if (correct) k_rs<false, true, false><<<g, kBlock, 0, st>>>(a);
-    else k_rs<false, false, true><<<g, kBlock, 0, st>>>(a);
-  }
+  // (a call with neither correct nor predict launches the predict form)
+  with_bools([&](auto LIBM, auto CORR, auto PRED) {
+    if constexpr (CORR() || PRED()) k_rs<LIBM(), CORR(), PRED()><<<g, kBlock, 0, st>>>(a);
+  }, libm, correct, predict || !correct);
   return (int)hipGetLastError();
 }
 

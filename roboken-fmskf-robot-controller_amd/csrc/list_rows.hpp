@@ -101,14 +101,11 @@ struct ListRegime {
   bool ok, ekf, comp, nt, big;
 };
 inline ListRegime list_regime(const DevState &s) {
-  static const bool force_big = [] {
-    const char *e = getenv("FMSKF_LIST_BIG");
-    return e && atoi(e) != 0;
-  }();
+  const bool force_big = FMSKF_ENV_INT("FMSKF_LIST_BIG", 0) != 0;
   const bool ekf = s.model == FMSKF_MODEL_EKF9, comp = s.xlo != nullptr;
   const bool ok = s.tile == tile_w<float>() && (ekf || s.model == FMSKF_MODEL_KF6) && !(ekf && (comp || !s.thlo));
   const bool big = force_big || (uint64_t)(ekf ? 45 : 21) * s.pitch * sizeof(float) > 0xFFFFFFFFull;
-  return {ok, ekf, comp, state_nt(ekf ? s.n * 55 * 4 : s.n * (comp ? 128 : 108)), big};
+  return {ok, ekf, comp, state_nt(s.n * (ekf ? ekf9_state_bytes(false) : kf6_state_bytes(comp))), big};
 }
 
 // with_bools for a list kernel: f(NX, COMP, CP, BIG, bools...) with the regime as compile-time

@@ -565,7 +565,7 @@ print("nt ok")
 def test_nontemporal_control_and_isr_bitexact():
     """The non-temporal control-state instantiations of k_ctrl_step and k_isr_rs, and the
     non-temporal motor-state CAN ingest k_can4<true> (chosen
-    automatically once the state outgrows the Infinity Cache, fmskf_internal.hpp state_nt)
+    automatically once the state outgrows the Infinity Cache, launch_regime.hpp state_nt)
     forced on at small N in a child process: the ISR and control parity tests above, against
     the three-call sequence and the oracle."""
     import os
