@@ -250,6 +250,79 @@ int fmskf_tick_many_smooth(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t
 int fmskf_smooth_workspace_bytes(fmskf_handle h, uint32_t n_ticks, uint64_t *bytes);
 int fmskf_smooth_reserve(fmskf_handle h, uint32_t n_ticks);   /* grow-only; 0 frees */
 
+/* ---- innovation log-likelihood of a replayed window (KF6) ---------------------- */
+/* How well a given Q and R explain a log: per robot, over the measured ticks of a window,
+ *     log L = -1/2 * sum_t ( NIS_t + log det S_t + 4 log 2 pi )
+ * the innovation (prediction-error) log-likelihood, the objective a Q / R fit maximises and the
+ * score that ranks candidate parameter sets; sum NIS / n_meas is the consistency check (4 for the
+ * four measurement rows of a consistent filter).  The call returns the three sums, so
+ * log L = -0.5 * (nis_sum + logdet_sum + n_meas * 4 log 2 pi).
+ *
+ * fmskf_tick_many_loglik takes the inputs of fmskf_tick_many (records or the three planes, an
+ * optional `valid` mask, host or device memory; explicit planes required).
+ * 1. It advances the handle exactly as fmskf_tick_many(h, in, n_ticks, tick_stride) would: x, P
+ *    and every counter are bit for bit what that call leaves (the non-finite guard counts in
+ *    counter [0] as that call's launch does).
+ * 2. For every tick that carries a measurement for the robot (`valid` NULL or non-zero), from the
+ *    state before the tick's update: y the innovation (the heading component wrapped as the update
+ *    wraps it); with S = H P H^T + R = L D L^T, w = L^-1 y and dinv = 1 / D the update's own
+ *    operands, NIS = the value of the chi-square gate (nis = w[0]*(w[0]*dinv[0]), then
+ *    fma(w[a], w[a]*dinv[a], nis), a = 1..3: what a monitor-only fmskf_set_gate reports, bit for
+ *    bit) and log det S = -sum_a log dinv[a].  A tick without a measurement contributes nothing.
+ * 3. The sums over the window are carried in registers, in fp32, with no transcendental per tick:
+ *    nis_sum as a compensated pair (every addition a TwoSum), stored as (double)hi + (double)lo;
+ *    logdet_sum as E * ln 2 + log(pm), where every dinv[a] is split exactly (frexp) into mantissa
+ *    and exponent, the four mantissas are multiplied as ((m0*m1)*m2)*m3, that product into the
+ *    running mantissa pm, pm is split again and all exponents are added to the int32 E: four
+ *    roundings of 2^-24 per measured tick in the log domain on top of dinv's own fp32 error, and
+ *    one fp64 log per robot at the store, logdet_sum = -((double)E * ln 2 + log((double)pm)).
+ *    innov_sum / innov_outer (either non-NULL selects the kernel variant that carries them): the
+ *    sums of y[a] and of the fp32 products y[i]*y[j], each a compensated fp32 pair like nis_sum,
+ *    stored as double.  csrc/loglik_lane.hpp; tests/loglik_ref.py holds the float64 definition
+ *    and the bound the results are held to.
+ *    A robot is left out when any dinv[a] of a measured tick is not a positive finite number or a
+ *    NIS is NaN: its nis_sum and logdet_sum are NaN, its n_meas is still the count, and it does
+ *    not enter `total`, whose [3] counts such robots.
+ * 4. total = { sum n_meas, sum nis_sum, sum logdet_sum, robots left out } over the robots not left
+ *    out, in fp64, deterministic: a fixed tree inside every 256-robot block, one partial per block
+ *    in a scratch the handle owns (allocated by the first call that asks for the total, freed by
+ *    fmskf_destroy; no checkpoint contains it), the partials added in block order by a second
+ *    small launch.  No floating-point atomics: two calls on the same state and inputs write the
+ *    same bytes everywhere.
+ * 5. FMSKF_LL_ACCUMULATE, for a log replayed in chunks: every per-robot output and every element
+ *    of total becomes old + new (one fp64 addition; n_meas an integer addition) instead of new.
+ *    The chunks advance the state as one call over the whole window does, bit for bit, as chunks
+ *    of fmskf_tick_many do.
+ * Every output pointer is optional, but not all of them.  Host outputs are mirrored on the device
+ * (the innovation planes at the caller's pitch) and copied out on the handle's stream, the
+ * caller's values copied in first with FMSKF_LL_ACCUMULATE; the call returns when they are
+ * complete, and elements past N of a padded row are left alone.  Device outputs are asynchronous
+ * on the handle's stream; the double arrays must be 8-byte aligned, n_meas 4-byte.
+ * fmskf_set_timing / fmskf_last_kernel_ms record the call's launches as one entry.
+ * 108 + 16 T bytes read and at most 108 + 20 written per robot, + 112 with the innovation sums.
+ *
+ * FMSKF_ENOTSUP: a model other than KF6, a handle with FMSKF_CFG_COMP_POS, a handle with a gate
+ * set (the smoother's exclusions).  FMSKF_EINVAL: out NULL, every output pointer NULL, unknown
+ * flags, a bad mem flag, pitch non-zero and below N, n_ticks == 0, a misaligned device output,
+ * everything fmskf_tick_many refuses, a call inside a graph capture.  FMSKF_ENOMEM: the scratch or
+ * the host staging cannot be allocated.  Each is raised before anything is launched, and the
+ * handle's state is untouched. */
+typedef struct fmskf_loglik_out {
+  uint32_t mem;        /* FMSKF_MEM_HOST or FMSKF_MEM_DEVICE for every pointer below */
+  uint32_t flags;      /* FMSKF_LL_* ; unknown bits: FMSKF_EINVAL */
+  uint64_t pitch;      /* innov_* planes: elements between rows; 0 = N, otherwise >= N */
+  uint32_t *n_meas;    /* [N] ticks of the window that carried a measurement for the robot */
+  double *nis_sum;     /* [N] sum of NIS over those ticks */
+  double *logdet_sum;  /* [N] sum of log det S over those ticks */
+  double *innov_sum;   /* [4][pitch]  sum of y (heading wrapped as the update wraps it); optional */
+  double *innov_outer; /* [10][pitch] sum of y y^T, packed lower triangle (k = i*(i+1)/2 + j); optional */
+  double *total;       /* [4] fleet: sum n_meas, sum nis_sum, sum logdet_sum, robots left out; optional */
+} fmskf_loglik_out;
+#define FMSKF_LL_ACCUMULATE 1u  /* add to what the caller's arrays (total included) hold, not overwrite */
+
+int fmskf_tick_many_loglik(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
+                           uint64_t tick_stride, const fmskf_loglik_out *out);
+
 /* ---- chi-square innovation gate (KF6) ---------------------------------------- */
 /* Off by default: a handle that never sets a gate runs the kernels and computes the bits it
  * always did, and writes the checkpoints it always wrote.

@@ -10,6 +10,7 @@
 //   api_select.cpp      fmskf_select, fmskf_get_state_subset / fmskf_set_state_subset
 //   api_range.cpp       fmskf_set_anchors / fmskf_get_anchors, fmskf_correct_range
 //   api_smooth.cpp      fmskf_tick_many_smooth and its workspace
+//   api_loglik.cpp      fmskf_tick_many_loglik
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -206,6 +207,10 @@ struct fmskf_ctx {
   // and no checkpoint holds it.
   void *smooth_ws = nullptr;
   size_t smooth_ws_bytes = 0;
+  // fmskf_tick_many_loglik: the blocks' partial fleet totals [4][ceil(N / 256)] (api_loglik.cpp),
+  // allocated by the first call that asks for the total.  Not state: every call writes what it
+  // reads, and no checkpoint holds it.
+  double *loglik_partial = nullptr;
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
   // call) that ran as the tick, control-step and frame kernels instead of one fused kernel
@@ -331,7 +336,11 @@ struct fmskf_ctx {
         oscratch_bytes = 0;
       }
       hipError_t e = hipMalloc(&oscratch, bytes);
-      if (e != hipSuccess) fmskf::capi::fail(FMSKF_ENOMEM, "output scratch hipMalloc failed");
+      if (e != hipSuccess) {
+        oscratch = nullptr;
+        (void)hipGetLastError();  // the next launch check must not see this allocation's error
+        fmskf::capi::fail(FMSKF_ENOMEM, "output scratch hipMalloc failed");
+      }
       oscratch_bytes = bytes;
     }
     return oscratch;
@@ -344,6 +353,7 @@ struct fmskf_ctx {
     if (stage) (void)hipFree(stage);
     if (oscratch) (void)hipFree(oscratch);
     if (smooth_ws) (void)hipFree(smooth_ws);
+    if (loglik_partial) (void)hipFree(loglik_partial);
     for (int k = 0; k < 2; k++) {
       if (pin_in[k]) (void)hipHostFree(pin_in[k]);
       if (pin_ev[k]) (void)hipEventDestroy(pin_ev[k]);

@@ -255,6 +255,16 @@ struct SmoothOut {
   float *x, *P;
   uint64_t pitch;
 };
+// fmskf_tick_many_loglik (kernels_loglik.hip; an argument struct of its own): the caller's outputs
+// as the kernel sees them (device pointers, any may be null).  pitch: the innovation planes' row
+// pitch in elements; partial [4][grid]: the blocks' partial totals in the handle's scratch, or null
+struct LoglikOut {
+  uint32_t *n_meas;
+  double *nis_sum, *logdet_sum, *innov_sum, *innov_outer;
+  uint64_t pitch;
+  double *partial;
+  uint32_t accumulate;  // FMSKF_LL_ACCUMULATE: old + new instead of new
+};
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -454,6 +464,11 @@ int launch_kf6_smooth_fwd(const DevState &s, const TickIn &in, const Kf6Params &
                           hipStream_t st);
 int launch_kf6_smooth_bwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,
                           const SmoothOut &out, hipStream_t st);
+// fmskf_tick_many_loglik (kernels_loglik.hip): the ticks of launch_kf6's tick_many with the window's
+// innovation sums stored behind the last one (plain ungated KF6 state only); with `total` (needs
+// out.partial) a second launch folds the blocks' partials into it
+int launch_kf6_loglik(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const LoglikOut &out,
+                      double *total, hipStream_t st);
 // the gate words unpacked into status [N], run [N], rejects [N] (device pointers, any may be null)
 int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
                        hipStream_t st);

@@ -85,6 +85,16 @@ class SmoothOut(C.Structure):
                 ("P", C.c_void_p)]
 
 
+# fmskf_tick_many_loglik: FMSKF_LL_ACCUMULATE (flag)
+LL_ACCUMULATE = 1
+
+
+class LoglikOut(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("flags", C.c_uint32), ("pitch", C.c_uint64), ("n_meas", C.c_void_p),
+                ("nis_sum", C.c_void_p), ("logdet_sum", C.c_void_p), ("innov_sum", C.c_void_p),
+                ("innov_outer", C.c_void_p), ("total", C.c_void_p)]
+
+
 class Gate(C.Structure):
     _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
 
@@ -163,6 +173,7 @@ SIGNATURES = {
     "fmskf_tick_many_smooth": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(SmoothOut)]),
     "fmskf_smooth_workspace_bytes": (C.c_int, [_H, C.c_uint32, C.POINTER(C.c_uint64)]),
     "fmskf_smooth_reserve": (C.c_int, [_H, C.c_uint32]),
+    "fmskf_tick_many_loglik": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(LoglikOut)]),
     "fmskf_get_pose": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_vel": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_state": (C.c_int, [_H, _P, _P, C.c_uint32]),

@@ -668,6 +668,64 @@ class Engine:
         grows); 0 frees it"""
         check(load().fmskf_smooth_reserve(self.h, int(n_ticks)), "smooth_reserve")
 
+    def tick_many_loglik(self, n_ticks, tick_stride=None, moments=False, total=False, accumulate_into=None, **kw):
+        """fmskf_tick_many_loglik (KF6): the ticks of tick_many, plus the window's innovation sums
+        per robot.  Returns a dict: n_meas [N] uint32, nis_sum [N] and logdet_sum [N] float64 (what
+        fmskf.loglik takes); with moments innov_sum [4, N] and innov_outer [10, N] (the sums of y
+        and of y y^T, packed lower triangle); with total the fleet's total [4] = sum n_meas, sum
+        nis_sum, sum logdet_sum, robots left out.  numpy inputs give numpy results; torch device
+        inputs give torch device results, asynchronous on the handle's stream.
+        accumulate_into: a dict of such arrays (an earlier call's result: a log replayed in chunks);
+        this call's sums are added to them (FMSKF_LL_ACCUMULATE) and the same arrays returned.  Its
+        keys select the outputs, its memory is the results' memory, and innovation planes wider
+        than N (a padded pitch) keep their elements past N."""
+        T = int(n_ticks)
+        stride = self.n if tick_stride is None else int(tick_stride)
+        ti, keep = self._inputs(kw, T, stride)
+        shapes = {"n_meas": (self.n,), "nis_sum": (self.n,), "logdet_sum": (self.n,), "innov_sum": (4, self.n),
+                  "innov_outer": (10, self.n), "total": (4,)}
+        lo = _lib.LoglikOut()
+        if accumulate_into is None:
+            names = ["n_meas", "nis_sum", "logdet_sum"] + (["innov_sum", "innov_outer"] if moments else []) + \
+                (["total"] if total else [])
+            if keep.mem == MEM_DEVICE:
+                import torch
+                dev = keep.keep[0].device
+                mk = lambda k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_meas" else torch.float64, device=dev)
+            else:
+                mk = lambda k: np.empty(shapes[k], np.uint32 if k == "n_meas" else np.float64)
+            out = {k: mk(k) for k in names}
+        else:
+            out = accumulate_into
+            lo.flags = _lib.LL_ACCUMULATE
+            if not out or set(out) - set(shapes):
+                raise ValueError(f"tick_many_loglik: accumulate_into needs some of {sorted(shapes)} and nothing else")
+        tor = [_is_torch(v) for v in out.values()]
+        if any(tor) != all(tor):
+            raise ValueError("tick_many_loglik: the outputs must live in the same memory")
+        cols = {int(out[k].shape[-1]) for k in ("innov_sum", "innov_outer") if k in out and len(out[k].shape) == 2}
+        if len(cols) > 1 or (cols and min(cols) < self.n):
+            raise ValueError("tick_many_loglik: innov_sum and innov_outer need one row pitch >= N")
+        pitch = cols.pop() if cols else self.n
+        for k, v in out.items():
+            want = shapes[k] if len(shapes[k]) == 1 else (shapes[k][0], pitch)
+            if tuple(v.shape) != want:
+                raise ValueError(f"tick_many_loglik: {k} has shape {tuple(v.shape)}, want {want}")
+            if tor[0]:
+                dt = "torch.float64" if k != "n_meas" else None
+                if not v.is_cuda or not v.is_contiguous() or (str(v.dtype) != dt if dt else v.element_size() != 4):
+                    raise TypeError(f"tick_many_loglik: a torch {k} must be a contiguous device tensor of "
+                                    f"{'float64' if dt else 'int32'}")
+            elif not isinstance(v, np.ndarray) or v.dtype != (np.uint32 if k == "n_meas" else np.float64) \
+                    or not v.flags.c_contiguous or not v.flags.writeable:
+                raise TypeError(f"tick_many_loglik: a host {k} must be a writable C-contiguous numpy array of "
+                                f"{'uint32' if k == 'n_meas' else 'float64'}")
+            setattr(lo, k, v.data_ptr() if tor[0] else v.ctypes.data)
+        lo.mem = MEM_DEVICE if tor[0] else MEM_HOST
+        lo.pitch = 0 if pitch == self.n else pitch
+        check(load().fmskf_tick_many_loglik(self.h, C.byref(ti), T, stride, C.byref(lo)), "tick_many_loglik")
+        return out
+
     # ------------------------------------------------------------------ readout
     def get_state(self):
         x = np.empty((self.nx, self.n), self.dtype)
@@ -1085,6 +1143,12 @@ def ensemble_combine(n_state: int, records) -> tuple[np.ndarray, np.ndarray]:
                                         mean.ctypes.data_as(C.c_void_p),
                                         cov.ctypes.data_as(C.c_void_p)), "ensemble_combine")
     return mean, cov
+
+
+def loglik(nis_sum, logdet_sum, n_meas):
+    """The innovation log-likelihood of Engine.tick_many_loglik's sums (per robot, or of the fleet's
+    total[1], total[2], total[0]): -0.5 * (nis + logdet + 4 * n * log(2 pi)).  numpy or torch."""
+    return -0.5 * (nis_sum + logdet_sum + 4.0 * n_meas * float(np.log(2.0 * np.pi)))
 
 
 def shard_span(n_total: int, world: int, rank: int) -> tuple[int, int]:
