@@ -323,6 +323,79 @@ typedef struct fmskf_loglik_out {
 int fmskf_tick_many_loglik(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
                            uint64_t tick_stride, const fmskf_loglik_out *out);
 
+/* ---- EM sufficient statistics for Q and R of a replayed window (KF6) ----------- */
+/* The smoother gives the states Q and R are fitted against, the log-likelihood the objective they
+ * are fitted by; this call gives the fit's step.  For a linear-Gaussian model the M-step of the EM
+ * algorithm is closed form: with w[t] = x[t+1] - F x[t] the process noise of the step t -> t+1 and
+ * v[t] = z[t] - H x[t] the measurement noise of a measured tick,
+ *     Q = sum_t E[w w^T | all T measurements] / n_trans,  R = sum_t E[v v^T | all] / n_meas
+ * under the smoothed distribution of the window.  With x_s, P_s the smoothed estimates of
+ * fmskf_tick_many_smooth and P_{t,t+1} = C P_s[t+1] the lag-one covariance (C that call's gain),
+ *     E[w w^T | all] = s s^T + P_s[t+1] - F P_{t,t+1} - P_{t,t+1}^T F^T + F P_s[t] F^T,
+ *                      s = x_s[t+1] - F x_s[t]                               (t = 0 .. T-2)
+ *     E[v v^T | all] = v v^T + H P_s[t] H^T,  v = z[t] - H x_s[t]            (measured t = 0 .. T-1)
+ * the heading components wrapped as the smoother and the update wrap them.  The kernels form the
+ * first in fp32 as s s^T + (Q - Q Pi Q) + (Pi Q)^T P_s[t+1] (Pi Q), Pi = (P-[t+1])^-1,
+ * s = Q Pi (x_s[t+1] - x-[t+1]): the same quantity as a sum of three positive semidefinite terms
+ * from the smoother's own operands, so that it does not cancel while a prior is still the diffuse
+ * P0 (csrc/em_lane.hpp).  Every tick's term is added to an fp64 accumulator: the sums do not lose
+ * accuracy with T.  tests/em_ref.py holds the float64 definition and the bound the results are
+ * held to.
+ *
+ * fmskf_tick_many_em takes the inputs of fmskf_tick_many (records or the three planes, an
+ * optional `valid` mask, host or device memory; explicit planes required).
+ * 1. It advances the handle exactly as fmskf_tick_many(h, in, n_ticks, tick_stride) would: x, P
+ *    and every counter are bit for bit what that call leaves.
+ * 2. Two launches and a small third for the total: fmskf_tick_many_smooth's forward pass into the
+ *    same workspace (fmskf_smooth_reserve, fmskf_smooth_workspace_bytes), then one backward pass
+ *    that writes nothing of size T: 124 B read per robot-tick, at most 4 + 31 * 8 B written per
+ *    robot.
+ * 3. sq [21][pitch]: per robot the sum over t = 0 .. T-2 of E[w w^T | all], packed lower triangle
+ *    (k = i*(i+1)/2 + j).  n_trans = T - 1 for every robot: the last predict of the window, from
+ *    tick T-1 to T, is not a term, and with T = 1 every sq entry is 0.  sr [10][pitch]: per robot
+ *    the sum over its measured ticks of E[v v^T | all]; n_meas [N] counts them.
+ * 4. A robot is left out when any of its 31 sums is not finite: its sq and sr are NaN, its n_meas
+ *    is still the count, and it enters neither the sums nor the counts of `total`.
+ * 5. total [34] = { sum n_trans, sum n_meas, robots left out, sq[21], sr[10] } over the robots not
+ *    left out, in fp64, deterministic like fmskf_tick_many_loglik's: a fixed tree inside every
+ *    256-robot block, one partial per quantity and block in a scratch the handle owns (allocated
+ *    by the first call that asks for the total, freed by fmskf_destroy; no checkpoint contains
+ *    it), the partials added in block order by a small launch.  No floating-point atomics: two
+ *    calls on the same state and inputs write the same bytes everywhere.
+ * 6. FMSKF_EM_ACCUMULATE: every per-robot output and every element of total becomes old + new (one
+ *    fp64 addition; n_meas an integer addition), so that several windows, or several logs, feed one
+ *    M-step.  Every call smooths its own window independently of the others: a log cut into two
+ *    windows is not the log smoothed as one, and the transition between two windows is not a term
+ *    of either.
+ * 7. fmskf_em_mstep, pure host: q[k] = total[3 + k] / total[0], r[k] = total[24 + k] / total[1], the
+ *    packed Q and R a new handle's fmskf_config takes.  FMSKF_EINVAL: a NULL argument, a non-finite
+ *    entry of total, total[0] <= 0 or total[1] <= 0.
+ * Every output pointer is optional, but not all of them.  Host outputs, their staging and
+ * FMSKF_EM_ACCUMULATE's copy-in behave as in fmskf_tick_many_loglik; device outputs are
+ * asynchronous on the handle's stream, the double arrays 8-byte aligned, n_meas 4-byte.
+ * fmskf_set_timing / fmskf_last_kernel_ms cover all launches of the call.
+ *
+ * FMSKF_ENOTSUP: the smoother's cases.  FMSKF_EINVAL: out NULL, every output pointer NULL, unknown
+ * flags, a bad mem flag, pitch non-zero and below N, n_ticks == 0, a misaligned device output,
+ * everything fmskf_tick_many refuses, a call inside a graph capture.  FMSKF_ENOMEM: the workspace,
+ * the scratch or the host staging cannot be allocated.  Each is raised before anything is
+ * launched, and the handle's state is untouched. */
+typedef struct fmskf_em_out {
+  uint32_t mem;      /* FMSKF_MEM_HOST or FMSKF_MEM_DEVICE for every pointer below */
+  uint32_t flags;    /* FMSKF_EM_ACCUMULATE; unknown bits: FMSKF_EINVAL */
+  uint64_t pitch;    /* sq / sr planes: elements between rows; 0 = N, otherwise >= N */
+  uint32_t *n_meas;  /* [N] measured ticks of the window; optional */
+  double *sq;        /* [21][pitch] per robot: sum over t = 0..T-2 of E[w w^T | all], packed lower triangle; optional */
+  double *sr;        /* [10][pitch] per robot: sum over measured t of (v v^T + H P_s[t] H^T); optional */
+  double *total;     /* [34] fleet: sum n_trans, sum n_meas, robots left out, sq[21], sr[10]; optional */
+} fmskf_em_out;
+#define FMSKF_EM_ACCUMULATE 1u  /* add to what the caller's arrays (total included) hold, not overwrite */
+#define FMSKF_EM_TOTAL_LEN 34u
+
+int fmskf_tick_many_em(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
+                       uint64_t tick_stride, const fmskf_em_out *out);
+int fmskf_em_mstep(const double *total, double *q /*[21]*/, double *r /*[10]*/);
+
 /* ---- chi-square innovation gate (KF6) ---------------------------------------- */
 /* Off by default: a handle that never sets a gate runs the kernels and computes the bits it
  * always did, and writes the checkpoints it always wrote.

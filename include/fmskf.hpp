@@ -136,6 +136,13 @@ class Robots {
     check(fmskf_tick_many_loglik(h_, in, n_ticks, tick_stride, &out), "fmskf_tick_many_loglik");
   }
 
+  // a replayed window of T ticks with the EM sufficient statistics for Q and R per robot, and the
+  // fleet's total, which fmskf_em_mstep divides, when out.total is set (fmskf_tick_many_em: KF6
+  // without a gate; the state is left as fmskf_tick_many leaves it)
+  void tick_many_em(const fmskf_tick_inputs *in, uint32_t n_ticks, uint64_t tick_stride, const fmskf_em_out &out) {
+    check(fmskf_tick_many_em(h_, in, n_ticks, tick_stride, &out), "fmskf_tick_many_em");
+  }
+
   // the robots for which any criterion of prm holds (fmskf_select: a state gone non-finite, a
   // position covariance above a threshold, a gate that keeps rejecting), strictly ascending --
   // the list correct_pose and the subset calls take.  robots / reason [capacity] (reason may be

@@ -11,6 +11,7 @@
 //   api_range.cpp       fmskf_set_anchors / fmskf_get_anchors, fmskf_correct_range
 //   api_smooth.cpp      fmskf_tick_many_smooth and its workspace
 //   api_loglik.cpp      fmskf_tick_many_loglik
+//   api_em.cpp          fmskf_tick_many_em, fmskf_em_mstep
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -211,6 +212,9 @@ struct fmskf_ctx {
   // allocated by the first call that asks for the total.  Not state: every call writes what it
   // reads, and no checkpoint holds it.
   double *loglik_partial = nullptr;
+  // fmskf_tick_many_em: the blocks' partial fleet totals [34][ceil(N / 256)] (api_em.cpp), as
+  // loglik_partial
+  double *em_partial = nullptr;
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
   // call) that ran as the tick, control-step and frame kernels instead of one fused kernel
@@ -354,6 +358,7 @@ struct fmskf_ctx {
     if (oscratch) (void)hipFree(oscratch);
     if (smooth_ws) (void)hipFree(smooth_ws);
     if (loglik_partial) (void)hipFree(loglik_partial);
+    if (em_partial) (void)hipFree(em_partial);
     for (int k = 0; k < 2; k++) {
       if (pin_in[k]) (void)hipHostFree(pin_in[k]);
       if (pin_ev[k]) (void)hipEventDestroy(pin_ev[k]);
@@ -495,6 +500,12 @@ bool ens_carry_plain();
 void ens_flush(fmskf_ctx *h);
 void ensure_shift(fmskf_ctx *h);
 bool fused_record(const fmskf_ctx *h);
+// api_smooth.cpp: the smoother's exclusions (FMSKF_ENOTSUP); the history of a window of n_ticks in
+// the handle's workspace, grown first if need be (FMSKF_ENOMEM, nothing launched); which pass the
+// timing events bracket (FMSKF_SMOOTH_TIME: 0 both, 1 forward, 2 backward)
+void check_smooth_model(const fmskf_ctx *h);
+SmoothHist smooth_hist(fmskf_ctx *h, uint32_t n_ticks);
+int smooth_timed_pass();
 // api_ctrl.cpp
 void ensure_ctrl(fmskf_ctx *h);
 void zero_ctrl(fmskf_ctx *h);

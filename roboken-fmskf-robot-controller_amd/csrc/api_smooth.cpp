@@ -6,15 +6,15 @@
 using namespace fmskf;
 using namespace fmskf::capi;
 
-namespace {
-
 // plain ungated KF6: the gate's accept / force decisions would have to be recorded per tick, and
 // the compensated positions have no smoother
-void check_smooth_model(const fmskf_ctx *h) {
+void fmskf::capi::check_smooth_model(const fmskf_ctx *h) {
   if (h->cfg.model != FMSKF_MODEL_KF6) fail(FMSKF_ENOTSUP, "smoothing is for KF6");
   if (h->cfg.flags & FMSKF_CFG_COMP_POS) fail(FMSKF_ENOTSUP, "smoothing is for KF6 without FMSKF_CFG_COMP_POS");
   if (h->gate_on) fail(FMSKF_ENOTSUP, "smoothing is for a KF6 handle without a gate (fmskf_set_gate)");
 }
+
+namespace {
 
 // the history of one tick in elements: x, then P, each tiled like the state (SmoothHist)
 struct Slice {
@@ -59,14 +59,19 @@ void ensure_workspace(fmskf_ctx *h, uint64_t bytes) {
   h->smooth_ws_bytes = bytes;
 }
 
-// FMSKF_SMOOTH_TIME (read per call; for tools/smooth_bench.py): "fwd" / "bwd" lets the timing
-// events bracket that pass alone; anything else, both passes
-int timed_pass() {
+}  // namespace
+
+// FMSKF_SMOOTH_TIME (read per call; for tools/smooth_bench.py, tools/em_bench.py): "fwd" / "bwd"
+// lets the timing events bracket that pass alone; anything else, both passes
+int fmskf::capi::smooth_timed_pass() {
   const char *e = env_knob("FMSKF_SMOOTH_TIME");
   return !e ? 0 : !strcmp(e, "fwd") ? 1 : !strcmp(e, "bwd") ? 2 : 0;
 }
 
-}  // namespace
+SmoothHist fmskf::capi::smooth_hist(fmskf_ctx *h, uint32_t n_ticks) {
+  ensure_workspace(h, workspace_bytes(h, n_ticks));
+  return hist_of(h);
+}
 
 extern "C" {
 
@@ -111,7 +116,7 @@ int fmskf_tick_many_smooth(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t
     // every allocation before the first launch: a failure leaves the state as it was
     const bool host = out->mem == FMSKF_MEM_HOST;
     const uint64_t pitch = out->pitch ? out->pitch : n;
-    ensure_workspace(h, workspace_bytes(h, n_ticks));
+    const SmoothHist hist = smooth_hist(h, n_ticks);
     const uint64_t xrow = bytes_mul(6 * n * sizeof(float), n_ticks), prow = bytes_mul(21 * n * sizeof(float), n_ticks);
     SmoothOut so{out->x, out->P, pitch};
     if (host) {  // dense [T][rows][N] on the device, copied out row by row at the caller's pitch
@@ -119,11 +124,10 @@ int fmskf_tick_many_smooth(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t
       char *stg = (char *)h->out_for(xrow + (out->P ? prow : 0));
       so = SmoothOut{(float *)stg, out->P ? (float *)(stg + xrow) : nullptr, n};
     }
-    const SmoothHist hist = hist_of(h);
     // a pending asynchronous ensemble event: its fold runs stand-alone, as ahead of fmskf_tick_many
     ens_flush(h);
     const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
-    const int only = timed_pass();
+    const int only = smooth_timed_pass();
     if (only != 2) h->time_begin();
     launch_check(launch_kf6_smooth_fwd(h->s, t, h->kf6, libm, hist, h->stream), "smoothing forward launch");
     if (only == 1) h->time_end();

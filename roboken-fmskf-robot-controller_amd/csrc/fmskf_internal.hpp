@@ -265,6 +265,16 @@ struct LoglikOut {
   double *partial;
   uint32_t accumulate;  // FMSKF_LL_ACCUMULATE: old + new instead of new
 };
+// fmskf_tick_many_em (kernels_em.hip; an argument struct of its own): the caller's outputs as the
+// kernel sees them (device pointers, any may be null).  pitch: the row pitch of sq [21] and sr [10]
+// in elements; partial [34][grid]: the blocks' partial totals in the handle's scratch, or null
+struct EmOut {
+  uint32_t *n_meas;
+  double *sq, *sr;
+  uint64_t pitch;
+  double *partial;
+  uint32_t accumulate;  // FMSKF_EM_ACCUMULATE: old + new instead of new
+};
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -469,6 +479,11 @@ int launch_kf6_smooth_bwd(const DevState &s, const TickIn &in, const Kf6Params &
 // out.partial) a second launch folds the blocks' partials into it
 int launch_kf6_loglik(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const LoglikOut &out,
                       double *total, hipStream_t st);
+// the backward pass of fmskf_tick_many_em (kernels_em.hip) behind launch_kf6_smooth_fwd: the EM
+// sums of the window, nothing [T]-sized; with `total` (needs out.partial) a second launch folds the
+// blocks' partials into it
+int launch_kf6_em_bwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,
+                      const EmOut &out, double *total, hipStream_t st);
 // the gate words unpacked into status [N], run [N], rejects [N] (device pointers, any may be null)
 int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
                        hipStream_t st);

@@ -129,6 +129,17 @@ __device__ __forceinline__ void smooth_solve6(const float (&L)[6][6], const floa
   }
 }
 
+// What SmoothCarry::back shows of its intermediates to a caller that needs them (em_lane.hpp: the
+// EM statistics are built from them); the smoother itself passes this one, whose calls are empty
+struct SmoothNoTap {
+  // s = Q Pi (x_s[t+1] - x-[t+1]), component i
+  __device__ __forceinline__ void resid(int, float) {}
+  // X = Pi Q, with Ps still P_s[t+1]
+  __device__ __forceinline__ void gain(const float (&)[6][6], const float (&)[21]) {}
+  // (Q - Q Pi Q)(i, j), j <= i
+  __device__ __forceinline__ void noise(int, int, float) {}
+};
+
 // The smoothed estimate of the tick behind the current one, carried down the window.  WP: P_s
 // exists (the call forms it)
 template <bool WP>
@@ -152,6 +163,12 @@ struct SmoothCarry {
   // innovation is.  The x path is the same operations with and without P_s.
   __device__ __forceinline__ void back(const float (&x1)[6], const float (&P1)[21], const float *Q, float dt,
                                        float (&e)[6]) {
+    SmoothNoTap tap;
+    back(x1, P1, Q, dt, e, tap);
+  }
+  template <class Tap>
+  __device__ __forceinline__ void back(const float (&x1)[6], const float (&P1)[21], const float *Q, float dt,
+                                       float (&e)[6], Tap &tap) {
     float L[6][6], dinv[6], d[6], pd[6];
     smooth_ldl6(P1, L, dinv);
 #pragma unroll
@@ -163,6 +180,7 @@ struct SmoothCarry {
       float s = Q[pk(i, 0)] * pd[0];
 #pragma unroll
       for (int k = 1; k < 6; k++) s = dfma(Q[pk(i, k)], pd[k], s);
+      tap.resid(i, s);
       e[i] = d[i] - s;
     }
 #pragma unroll
@@ -182,6 +200,7 @@ struct SmoothCarry {
 #pragma unroll
         for (int k = 0; k < 6; k++) X[k][j] = c[k];
       }
+      tap.gain(X, P);
       float A[6][6];  // I - Q Pi = I - X^T
 #pragma unroll
       for (int i = 0; i < 6; i++) {
@@ -208,6 +227,7 @@ struct SmoothCarry {
 #pragma unroll
           for (int k = 1; k < 6; k++) s = dfma(Q[pk(i, k)], X[k][j], s);
           s = Q[pk(i, j)] - s;
+          tap.noise(i, j, s);
 #pragma unroll
           for (int l = 0; l < 6; l++) s = dfma(M[i][l], A[j][l], s);
           G[pk(i, j)] = s;

@@ -95,6 +95,16 @@ class LoglikOut(C.Structure):
                 ("innov_outer", C.c_void_p), ("total", C.c_void_p)]
 
 
+# fmskf_tick_many_em: FMSKF_EM_ACCUMULATE (flag), FMSKF_EM_TOTAL_LEN
+EM_ACCUMULATE = 1
+EM_TOTAL_LEN = 34
+
+
+class EmOut(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("flags", C.c_uint32), ("pitch", C.c_uint64), ("n_meas", C.c_void_p),
+                ("sq", C.c_void_p), ("sr", C.c_void_p), ("total", C.c_void_p)]
+
+
 class Gate(C.Structure):
     _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
 
@@ -174,6 +184,8 @@ SIGNATURES = {
     "fmskf_smooth_workspace_bytes": (C.c_int, [_H, C.c_uint32, C.POINTER(C.c_uint64)]),
     "fmskf_smooth_reserve": (C.c_int, [_H, C.c_uint32]),
     "fmskf_tick_many_loglik": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(LoglikOut)]),
+    "fmskf_tick_many_em": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(EmOut)]),
+    "fmskf_em_mstep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "fmskf_get_pose": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_vel": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_state": (C.c_int, [_H, _P, _P, C.c_uint32]),

@@ -726,6 +726,65 @@ class Engine:
         check(load().fmskf_tick_many_loglik(self.h, C.byref(ti), T, stride, C.byref(lo)), "tick_many_loglik")
         return out
 
+    def tick_many_em(self, n_ticks, tick_stride=None, per_robot=False, total=True, accumulate_into=None, **kw):
+        """fmskf_tick_many_em (KF6): the ticks of tick_many, plus the EM sufficient statistics for Q
+        and R of the smoothed window.  Returns a dict: with total the fleet's total [34] = sum
+        n_trans, sum n_meas, robots left out, sq [21], sr [10] (what fmskf.em_mstep takes); with
+        per_robot n_meas [N] uint32, sq [21, N] and sr [10, N] float64 (packed lower triangles).
+        numpy inputs give numpy results; torch device inputs give torch device results,
+        asynchronous on the handle's stream.
+        accumulate_into: a dict of such arrays (an earlier call's result: another window, another
+        log); this call's sums are added to them (FMSKF_EM_ACCUMULATE) and the same arrays
+        returned.  Its keys select the outputs, its memory is the results' memory, and sq / sr
+        planes wider than N (a padded pitch) keep their elements past N.  Every call smooths its
+        own window: the transition between two windows is not a term."""
+        T = int(n_ticks)
+        stride = self.n if tick_stride is None else int(tick_stride)
+        ti, keep = self._inputs(kw, T, stride)
+        shapes = {"n_meas": (self.n,), "sq": (21, self.n), "sr": (10, self.n), "total": (_lib.EM_TOTAL_LEN,)}
+        eo = _lib.EmOut()
+        if accumulate_into is None:
+            names = (["n_meas", "sq", "sr"] if per_robot else []) + (["total"] if total else [])
+            if not names:
+                raise ValueError("tick_many_em: neither per_robot nor total")
+            if keep.mem == MEM_DEVICE:
+                import torch
+                dev = keep.keep[0].device
+                mk = lambda k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_meas" else torch.float64, device=dev)
+            else:
+                mk = lambda k: np.empty(shapes[k], np.uint32 if k == "n_meas" else np.float64)
+            out = {k: mk(k) for k in names}
+        else:
+            out = accumulate_into
+            eo.flags = _lib.EM_ACCUMULATE
+            if not out or set(out) - set(shapes):
+                raise ValueError(f"tick_many_em: accumulate_into needs some of {sorted(shapes)} and nothing else")
+        tor = [_is_torch(v) for v in out.values()]
+        if any(tor) != all(tor):
+            raise ValueError("tick_many_em: the outputs must live in the same memory")
+        cols = {int(out[k].shape[-1]) for k in ("sq", "sr") if k in out and len(out[k].shape) == 2}
+        if len(cols) > 1 or (cols and min(cols) < self.n):
+            raise ValueError("tick_many_em: sq and sr need one row pitch >= N")
+        pitch = cols.pop() if cols else self.n
+        for k, v in out.items():
+            want = shapes[k] if len(shapes[k]) == 1 else (shapes[k][0], pitch)
+            if tuple(v.shape) != want:
+                raise ValueError(f"tick_many_em: {k} has shape {tuple(v.shape)}, want {want}")
+            if tor[0]:
+                dt = "torch.float64" if k != "n_meas" else None
+                if not v.is_cuda or not v.is_contiguous() or (str(v.dtype) != dt if dt else v.element_size() != 4):
+                    raise TypeError(f"tick_many_em: a torch {k} must be a contiguous device tensor of "
+                                    f"{'float64' if dt else 'int32'}")
+            elif not isinstance(v, np.ndarray) or v.dtype != (np.uint32 if k == "n_meas" else np.float64) \
+                    or not v.flags.c_contiguous or not v.flags.writeable:
+                raise TypeError(f"tick_many_em: a host {k} must be a writable C-contiguous numpy array of "
+                                f"{'uint32' if k == 'n_meas' else 'float64'}")
+            setattr(eo, k, v.data_ptr() if tor[0] else v.ctypes.data)
+        eo.mem = MEM_DEVICE if tor[0] else MEM_HOST
+        eo.pitch = 0 if pitch == self.n else pitch
+        check(load().fmskf_tick_many_em(self.h, C.byref(ti), T, stride, C.byref(eo)), "tick_many_em")
+        return out
+
     # ------------------------------------------------------------------ readout
     def get_state(self):
         x = np.empty((self.nx, self.n), self.dtype)
@@ -1149,6 +1208,23 @@ def loglik(nis_sum, logdet_sum, n_meas):
     """The innovation log-likelihood of Engine.tick_many_loglik's sums (per robot, or of the fleet's
     total[1], total[2], total[0]): -0.5 * (nis + logdet + 4 * n * log(2 pi)).  numpy or torch."""
     return -0.5 * (nis_sum + logdet_sum + 4.0 * n_meas * float(np.log(2.0 * np.pi)))
+
+
+def em_mstep(total):
+    """fmskf_em_mstep: the M-step of Engine.tick_many_em's fleet total [34] (a numpy array, or a
+    torch tensor, which is copied to the host): (q [21], r [10]), the packed Q and R a new
+    Engine(q=, r=) takes.  FMSKF_EINVAL for a total without transitions or measurements or with a
+    non-finite entry."""
+    if total is None:
+        tp = None
+    else:
+        t = np.ascontiguousarray(total.cpu().numpy() if _is_torch(total) else total, np.float64)
+        if t.shape != (_lib.EM_TOTAL_LEN,):
+            raise ValueError(f"em_mstep: total has shape {t.shape}, want {(_lib.EM_TOTAL_LEN,)}")
+        tp = t.ctypes.data
+    q, r = np.empty(21, np.float64), np.empty(10, np.float64)
+    check(load().fmskf_em_mstep(tp, q.ctypes.data, r.ctypes.data), "em_mstep")
+    return q, r
 
 
 def shard_span(n_total: int, world: int, rank: int) -> tuple[int, int]:
