@@ -12,6 +12,9 @@
 //   api_smooth.cpp      fmskf_tick_many_smooth and its workspace
 //   api_loglik.cpp      fmskf_tick_many_loglik
 //   api_em.cpp          fmskf_tick_many_em, fmskf_em_mstep
+// The three window calls share their front end, at the end of this header: the model check, the
+// call opening (window_call), bytes_mul, ensure_partial, the staging of host outputs from a piece
+// table (window_pieces.hpp: the table and its plan, host only) and the bracketing of two passes.
 #pragma once
 #include "../../include/fmskf.h"
 
@@ -27,6 +30,7 @@
 #include <vector>
 
 #include "fmskf_internal.hpp"
+#include "window_pieces.hpp"
 
 namespace fmskf {
 namespace capi {
@@ -208,12 +212,11 @@ struct fmskf_ctx {
   // and no checkpoint holds it.
   void *smooth_ws = nullptr;
   size_t smooth_ws_bytes = 0;
-  // fmskf_tick_many_loglik: the blocks' partial fleet totals [4][ceil(N / 256)] (api_loglik.cpp),
+  // fmskf_tick_many_loglik: the blocks' partial fleet totals [4][ceil(N / 256)] (ensure_partial),
   // allocated by the first call that asks for the total.  Not state: every call writes what it
   // reads, and no checkpoint holds it.
   double *loglik_partial = nullptr;
-  // fmskf_tick_many_em: the blocks' partial fleet totals [34][ceil(N / 256)] (api_em.cpp), as
-  // loglik_partial
+  // fmskf_tick_many_em: the blocks' partial fleet totals [34][ceil(N / 256)], as loglik_partial
   double *em_partial = nullptr;
   // which launch form the firmware-ISR calls took (fmskf_get_counters [1], [2]): calls of
   // fmskf_isr_tick_can that ran the CAN RX as its own kernel before the ISR, and ISRs (of either
@@ -500,17 +503,117 @@ bool ens_carry_plain();
 void ens_flush(fmskf_ctx *h);
 void ensure_shift(fmskf_ctx *h);
 bool fused_record(const fmskf_ctx *h);
-// api_smooth.cpp: the smoother's exclusions (FMSKF_ENOTSUP); the history of a window of n_ticks in
-// the handle's workspace, grown first if need be (FMSKF_ENOMEM, nothing launched); which pass the
-// timing events bracket (FMSKF_SMOOTH_TIME: 0 both, 1 forward, 2 backward)
-void check_smooth_model(const fmskf_ctx *h);
+// api_smooth.cpp: the history of a window of n_ticks in the handle's workspace, grown first if
+// need be (FMSKF_ENOMEM, nothing launched)
 SmoothHist smooth_hist(fmskf_ctx *h, uint32_t n_ticks);
-int smooth_timed_pass();
 // api_ctrl.cpp
 void ensure_ctrl(fmskf_ctx *h);
 void zero_ctrl(fmskf_ctx *h);
 // form the control step's derived outputs if the last step left them (ctrl_derived_stale)
 void ctrl_materialize(fmskf_ctx *h);
+
+// ---------------------------------------------------------------------------
+// The calls that replay a window of KF6 ticks (api_smooth.cpp, api_loglik.cpp, api_em.cpp): one
+// front end.  Every call checks in the order model, its own output struct (null, empty, flags),
+// then window_call's: mem, pitch, n_ticks, alignment, capture, inputs; then every allocation
+// before the first launch -- a failure leaves the state as it was -- ens_flush, the launches.
+// ---------------------------------------------------------------------------
+
+// plain ungated KF6: a gate's accept / force decisions would have to be recorded per tick (and its
+// rejected ticks leave the sums), and the compensated positions have their own update and no
+// smoother.  what: "smoothing is", "the innovation log-likelihood is"
+inline void check_window_model(const fmskf_ctx *h, const char *what) {
+  const std::string w(what);
+  if (h->cfg.model != FMSKF_MODEL_KF6) fail(FMSKF_ENOTSUP, w + " for KF6");
+  if (h->cfg.flags & FMSKF_CFG_COMP_POS) fail(FMSKF_ENOTSUP, w + " for KF6 without FMSKF_CFG_COMP_POS");
+  if (h->gate_on) fail(FMSKF_ENOTSUP, w + " for a KF6 handle without a gate (fmskf_set_gate)");
+}
+
+// a * b bytes, or FMSKF_ENOMEM "<what> too large" when no allocation could hold it
+inline uint64_t bytes_mul(uint64_t a, uint64_t b, const char *what) {
+  uint64_t r;
+  if (!bytes_fit(a, b, &r)) fail(FMSKF_ENOMEM, std::string(what) + " too large");
+  return r;
+}
+
+// The common checks of a window call once its output struct's mem and pitch are known (misaligned:
+// a device output the kernels could not store to), both capture refusals, the device, the input
+// forms and checks of fmskf_tick_many (host inputs are staged, nothing is launched); then body(t).
+// name: the entry point, what: the call's noun ("smoothing", "log-likelihood", "EM")
+template <class F>
+void window_call(fmskf_ctx *h, const char *name, const char *what, uint32_t mem, uint64_t pitch, bool misaligned,
+                 const fmskf_tick_inputs *in, uint32_t n_ticks, uint64_t tick_stride, F &&body) {
+  const std::string w(what), captured = std::string(name) + " cannot be captured";
+  if (mem != FMSKF_MEM_HOST && mem != FMSKF_MEM_DEVICE) fail(FMSKF_EINVAL, "bad mem flag");
+  if (pitch && pitch < h->s.n) fail(FMSKF_EINVAL, w + " output pitch < N");
+  if (n_ticks == 0) fail(FMSKF_EINVAL, "n_ticks == 0");
+  if (mem == FMSKF_MEM_DEVICE && misaligned) fail(FMSKF_EINVAL, "misaligned " + w + " device output");
+  if (h->capturing) fail(FMSKF_EINVAL, captured);
+  DeviceGuard g(h->cfg.device);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (h->stream && hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    fail(FMSKF_EINVAL, captured);
+  TickIn t = resolve_inputs(h, in, true, true, n_ticks, tick_stride);
+  body(t);
+}
+
+// the blocks' partial fleet totals [K][ceil(N / 256)] in the handle's `slot`: allocated on the first
+// call that asks for the total, freed with the handle (N is fixed, so it never grows)
+inline double *ensure_partial(fmskf_ctx *h, double **slot, size_t K, const char *what) {
+  if (!*slot) {
+    const size_t blocks = (size_t)((h->s.n + kBlock - 1) / kBlock);
+    const hipError_t e = hipMalloc((void **)slot, K * blocks * sizeof(double));
+    if (e != hipSuccess) {
+      *slot = nullptr;
+      (void)hipGetLastError();  // the next launch check must not see this allocation's error
+      fail(FMSKF_ENOMEM, std::string(what) + " scratch hipMalloc: " + hipGetErrorString(e));
+    }
+  }
+  return *slot;
+}
+
+// The piece table of a call with host outputs (window_pieces.hpp): the device mirror in the
+// handle's output scratch (FMSKF_ENOMEM, nothing launched), the caller's values staged in for an
+// accumulating call, the results copied out behind the launches.
+inline char *stage_pieces(fmskf_ctx *h, Piece *pc, int count, const char *what) {
+  uint64_t bytes;
+  if (!plan_pieces(pc, count, &bytes)) fail(FMSKF_ENOMEM, std::string(what) + " output staging too large");
+  return (char *)h->out_for(bytes);
+}
+template <class T>
+T *piece_at(char *stg, const Piece &p) {
+  return p.user ? (T *)(stg + p.off) : nullptr;
+}
+inline void pieces_in(fmskf_ctx *h, const Piece *pc, int count, const char *what) {
+  const std::string msg = std::string(what) + " outputs H2D";
+  for (int k = 0; k < count; k++)
+    if (pc[k].user)
+      hip_check(hipMemcpy2DAsync((char *)h->oscratch + pc[k].off, pc[k].step_bytes(), pc[k].user, pc[k].step_bytes(),
+                                 pc[k].row_bytes(), pc[k].rows, hipMemcpyHostToDevice, h->stream), msg.c_str());
+}
+inline void pieces_out(fmskf_ctx *h, const Piece *pc, int count, const char *what) {
+  const std::string msg = std::string(what) + " outputs D2H";
+  for (int k = 0; k < count; k++)
+    if (pc[k].user)
+      hip_check(hipMemcpy2DAsync(pc[k].user, pc[k].step_bytes(), (char *)h->oscratch + pc[k].off, pc[k].step_bytes(),
+                                 pc[k].row_bytes(), pc[k].rows, hipMemcpyDeviceToHost, h->stream), msg.c_str());
+  finish_out(h, FMSKF_MEM_HOST);
+}
+
+// The forward and the backward launch of a smoothed window between the timing events.
+// FMSKF_SMOOTH_TIME (read per call; for tools/smooth_bench.py, tools/em_bench.py): "fwd" / "bwd"
+// lets the events bracket that pass alone; anything else, both passes
+template <class F, class B>
+void timed_passes(fmskf_ctx *h, F &&fwd, B &&bwd) {
+  const char *e = env_knob("FMSKF_SMOOTH_TIME");
+  const int only = !e ? 0 : !strcmp(e, "fwd") ? 1 : !strcmp(e, "bwd") ? 2 : 0;
+  if (only != 2) h->time_begin();
+  fwd();
+  if (only == 1) h->time_end();
+  if (only == 2) h->time_begin();
+  bwd();
+  if (only != 1) h->time_end();
+}
 
 }  // namespace capi
 }  // namespace fmskf

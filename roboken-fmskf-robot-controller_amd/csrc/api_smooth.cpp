@@ -1,18 +1,11 @@
 // api_smooth.cpp -- fixed-interval smoothing of a replayed window of KF6 ticks:
-// fmskf_tick_many_smooth (argument checks, the workspace, staging of host outputs, the two
-// launches of kernels_smooth.hip), fmskf_smooth_workspace_bytes and fmskf_smooth_reserve.
+// fmskf_tick_many_smooth (its own argument checks, the workspace, staging of host outputs, the two
+// launches of kernels_smooth.hip; the front end of the window calls is api_ctx.hpp's),
+// fmskf_smooth_workspace_bytes and fmskf_smooth_reserve.
 #include "api_ctx.hpp"
 
 using namespace fmskf;
 using namespace fmskf::capi;
-
-// plain ungated KF6: the gate's accept / force decisions would have to be recorded per tick, and
-// the compensated positions have no smoother
-void fmskf::capi::check_smooth_model(const fmskf_ctx *h) {
-  if (h->cfg.model != FMSKF_MODEL_KF6) fail(FMSKF_ENOTSUP, "smoothing is for KF6");
-  if (h->cfg.flags & FMSKF_CFG_COMP_POS) fail(FMSKF_ENOTSUP, "smoothing is for KF6 without FMSKF_CFG_COMP_POS");
-  if (h->gate_on) fail(FMSKF_ENOTSUP, "smoothing is for a KF6 handle without a gate (fmskf_set_gate)");
-}
 
 namespace {
 
@@ -29,14 +22,9 @@ SmoothHist hist_of(const fmskf_ctx *h) {
   const Slice s = slice_of(h);
   return {(float *)h->smooth_ws, (float *)h->smooth_ws + s.sx, s.sx + s.sp, s.sx + s.sp};
 }
-// a * b bytes, or FMSKF_ENOMEM when no allocation could hold it
-uint64_t bytes_mul(uint64_t a, uint64_t b) {
-  if (b && a > (uint64_t)SIZE_MAX / b) fail(FMSKF_ENOMEM, "smoothing window too large");
-  return a * b;
-}
 uint64_t workspace_bytes(const fmskf_ctx *h, uint32_t n_ticks) {
   const Slice s = slice_of(h);
-  return bytes_mul((s.sx + s.sp) * sizeof(float), n_ticks);
+  return bytes_mul((s.sx + s.sp) * sizeof(float), n_ticks, "smoothing window");
 }
 
 void free_workspace(fmskf_ctx *h) {
@@ -61,13 +49,6 @@ void ensure_workspace(fmskf_ctx *h, uint64_t bytes) {
 
 }  // namespace
 
-// FMSKF_SMOOTH_TIME (read per call; for tools/smooth_bench.py, tools/em_bench.py): "fwd" / "bwd"
-// lets the timing events bracket that pass alone; anything else, both passes
-int fmskf::capi::smooth_timed_pass() {
-  const char *e = env_knob("FMSKF_SMOOTH_TIME");
-  return !e ? 0 : !strcmp(e, "fwd") ? 1 : !strcmp(e, "bwd") ? 2 : 0;
-}
-
 SmoothHist fmskf::capi::smooth_hist(fmskf_ctx *h, uint32_t n_ticks) {
   ensure_workspace(h, workspace_bytes(h, n_ticks));
   return hist_of(h);
@@ -78,7 +59,7 @@ extern "C" {
 int fmskf_smooth_workspace_bytes(fmskf_handle h, uint32_t n_ticks, uint64_t *bytes) {
   return guarded([&] {
     check_handle(h);
-    check_smooth_model(h);
+    check_window_model(h, "smoothing is");
     if (!bytes) fail(FMSKF_EINVAL, "null bytes");
     *bytes = workspace_bytes(h, n_ticks);
   });
@@ -87,7 +68,7 @@ int fmskf_smooth_workspace_bytes(fmskf_handle h, uint32_t n_ticks, uint64_t *byt
 int fmskf_smooth_reserve(fmskf_handle h, uint32_t n_ticks) {
   return guarded([&] {
     check_handle(h);
-    check_smooth_model(h);
+    check_window_model(h, "smoothing is");
     if (h->capturing) fail(FMSKF_EINVAL, "the smoothing workspace cannot change inside a graph capture");
     DeviceGuard g(h->cfg.device);
     if (n_ticks == 0) free_workspace(h);
@@ -99,50 +80,43 @@ int fmskf_tick_many_smooth(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t
                            uint64_t tick_stride, const fmskf_smooth_out *out) {
   return guarded([&] {
     check_handle(h);
-    check_smooth_model(h);
+    check_window_model(h, "smoothing is");
     const uint64_t n = h->s.n;
     if (!out || !out->x) fail(FMSKF_EINVAL, "null smoothing output");
     if (out->reserved) fail(FMSKF_EINVAL, "fmskf_smooth_out.reserved must be 0");
-    if (out->mem != FMSKF_MEM_HOST && out->mem != FMSKF_MEM_DEVICE) fail(FMSKF_EINVAL, "bad mem flag");
-    if (out->pitch && out->pitch < n) fail(FMSKF_EINVAL, "smoothing output pitch < N");
-    if (n_ticks == 0) fail(FMSKF_EINVAL, "n_ticks == 0");
-    if (h->capturing) fail(FMSKF_EINVAL, "fmskf_tick_many_smooth cannot be captured");
-    DeviceGuard g(h->cfg.device);
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (h->stream && hipStreamIsCapturing(h->stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-      fail(FMSKF_EINVAL, "fmskf_tick_many_smooth cannot be captured");
-    // the input forms and checks of fmskf_tick_many; host inputs are staged, nothing is launched
-    TickIn t = resolve_inputs(h, in, true, true, n_ticks, tick_stride);
-    // every allocation before the first launch: a failure leaves the state as it was
-    const bool host = out->mem == FMSKF_MEM_HOST;
-    const uint64_t pitch = out->pitch ? out->pitch : n;
-    const SmoothHist hist = smooth_hist(h, n_ticks);
-    const uint64_t xrow = bytes_mul(6 * n * sizeof(float), n_ticks), prow = bytes_mul(21 * n * sizeof(float), n_ticks);
-    SmoothOut so{out->x, out->P, pitch};
-    if (host) {  // dense [T][rows][N] on the device, copied out row by row at the caller's pitch
-      if (out->P && xrow > (uint64_t)SIZE_MAX - prow) fail(FMSKF_ENOMEM, "smoothing window too large");
-      char *stg = (char *)h->out_for(xrow + (out->P ? prow : 0));
-      so = SmoothOut{(float *)stg, out->P ? (float *)(stg + xrow) : nullptr, n};
-    }
-    // a pending asynchronous ensemble event: its fold runs stand-alone, as ahead of fmskf_tick_many
-    ens_flush(h);
-    const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
-    const int only = smooth_timed_pass();
-    if (only != 2) h->time_begin();
-    launch_check(launch_kf6_smooth_fwd(h->s, t, h->kf6, libm, hist, h->stream), "smoothing forward launch");
-    if (only == 1) h->time_end();
-    if (only == 2) h->time_begin();
-    launch_check(launch_kf6_smooth_bwd(h->s, t, h->kf6, libm, hist, so, h->stream), "smoothing backward launch");
-    if (only != 1) h->time_end();
-    if (host) {
-      const size_t row = (size_t)n * sizeof(float), dp = (size_t)pitch * sizeof(float);
-      hip_check(hipMemcpy2DAsync(out->x, dp, so.x, row, row, (size_t)6 * n_ticks, hipMemcpyDeviceToHost, h->stream),
-                "smoothed x D2H");
-      if (out->P)
-        hip_check(hipMemcpy2DAsync(out->P, dp, so.P, row, row, (size_t)21 * n_ticks, hipMemcpyDeviceToHost, h->stream),
-                  "smoothed P D2H");
-      finish_out(h, out->mem);
-    }
+    window_call(h, "fmskf_tick_many_smooth", "smoothing", out->mem, out->pitch, false, in, n_ticks, tick_stride,
+                [&](const TickIn &t) {
+      const bool host = out->mem == FMSKF_MEM_HOST;
+      const uint64_t pitch = out->pitch ? out->pitch : n;
+      const SmoothHist hist = smooth_hist(h, n_ticks);
+      const uint64_t xrow = bytes_mul(6 * n * sizeof(float), n_ticks, "smoothing window"),
+                     prow = bytes_mul(21 * n * sizeof(float), n_ticks, "smoothing window");
+      SmoothOut so{out->x, out->P, pitch};
+      // Dense [T][rows][N] on the device, copied out row by row at the caller's pitch: not a piece
+      // table (window_pieces.hpp), whose mirror has the caller's pitch on both sides
+      if (host) {
+        if (out->P && xrow > (uint64_t)SIZE_MAX - prow) fail(FMSKF_ENOMEM, "smoothing window too large");
+        char *stg = (char *)h->out_for(xrow + (out->P ? prow : 0));
+        so = SmoothOut{(float *)stg, out->P ? (float *)(stg + xrow) : nullptr, n};
+      }
+      // a pending asynchronous ensemble event: its fold runs stand-alone, as ahead of fmskf_tick_many
+      ens_flush(h);
+      const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
+      timed_passes(h, [&] {
+        launch_check(launch_kf6_smooth_fwd(h->s, t, h->kf6, libm, hist, h->stream), "smoothing forward launch");
+      }, [&] {
+        launch_check(launch_kf6_smooth_bwd(h->s, t, h->kf6, libm, hist, so, h->stream), "smoothing backward launch");
+      });
+      if (host) {
+        const size_t row = (size_t)n * sizeof(float), dp = (size_t)pitch * sizeof(float);
+        hip_check(hipMemcpy2DAsync(out->x, dp, so.x, row, row, (size_t)6 * n_ticks, hipMemcpyDeviceToHost, h->stream),
+                  "smoothed x D2H");
+        if (out->P)
+          hip_check(hipMemcpy2DAsync(out->P, dp, so.P, row, row, (size_t)21 * n_ticks, hipMemcpyDeviceToHost, h->stream),
+                    "smoothed P D2H");
+        finish_out(h, out->mem);
+      }
+    });
   });
 }
 

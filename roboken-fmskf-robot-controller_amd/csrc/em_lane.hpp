@@ -21,6 +21,7 @@
 // inside 64 KiB of static LDS, two blocks per CU.  tests/em_ref.py restates the order in numpy.
 #pragma once
 #include "smooth_lane.hpp"
+#include "window_lane.hpp"
 
 #pragma clang fp contract(off)
 
@@ -102,19 +103,9 @@ struct EmTap {
   __device__ __forceinline__ void noise(int i, int j, float v) { acc.add(pk(i, j), v); }
 };
 
-// one value of a per-robot plane at the lane's slot of its 256-robot chunk: overwritten, or with
-// FMSKF_EM_ACCUMULATE old + new
-template <typename T>
-__device__ __forceinline__ void em_put(T *plane, uint32_t hb, uint64_t n, uint32_t li, bool acc, T v) {
-  if (acc) v = ld_chunk<T, 0>(plane, hb, n, li) + v;
-  st_chunk<T, st_pol(0)>(plane, hb, n, li, v);
-}
-
 // The stores after tick 0 (ic: the lane's clamped robot, its chunk wave-uniform), then the block's
-// partial totals: the lanes' fp64 values (zeros for a dead lane and for a robot left out, which
-// counts in [2]) through a fixed butterfly inside each wave -- every lane ends with the same sum,
-// since a + b is b + a -- and the four waves' sums added in wave order, one thread per quantity.
-// red: [wave][quantity].
+// partial totals (window_lane.hpp block_partials) of the lanes' fp64 values: zeros for a dead lane
+// and for a robot left out, which counts in [2].  red: [wave][quantity].
 __device__ __forceinline__ void em_store(const EmOut &o, uint64_t n, uint32_t ic, bool live, uint32_t n_trans,
                                          const EmAcc &c, double (*red)[kEmTotal]) {
   const uint32_t hb = gate_chunk(ic), li = ic - hb;
@@ -127,33 +118,24 @@ __device__ __forceinline__ void em_store(const EmOut &o, uint64_t n, uint32_t ic
   }
   const double nan = __builtin_nan("");
   if (live) {
-    if (o.n_meas) em_put<uint32_t>(o.n_meas, hb, n, li, acc, c.n_meas);
+    if (o.n_meas) window_put<uint32_t>(o.n_meas, hb, n, li, acc, c.n_meas);
     if (o.sq) {
 #pragma unroll
-      for (int k = 0; k < kEmQ; k++) em_put<double>(o.sq + (uint64_t)k * o.pitch, hb, n, li, acc, bad ? nan : c.get(k));
+      for (int k = 0; k < kEmQ; k++)
+        window_put<double>(o.sq + (uint64_t)k * o.pitch, hb, n, li, acc, bad ? nan : c.get(k));
     }
     if (o.sr) {
 #pragma unroll
       for (int k = 0; k < kEmR; k++)
-        em_put<double>(o.sr + (uint64_t)k * o.pitch, hb, n, li, acc, bad ? nan : c.get(kEmQ + k));
+        window_put<double>(o.sr + (uint64_t)k * o.pitch, hb, n, li, acc, bad ? nan : c.get(kEmQ + k));
     }
   }
   if (o.partial) {
     const bool in = live && !bad;
-    const int w = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kEmTotal; k++) {
-      double v = k == 0 ? (double)n_trans : k == 1 ? (double)c.n_meas : k == 2 ? 1.0 : c.get(k - 3);
-      v = (k == 2 ? live && bad : in) ? v : 0.0;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) v = v + __shfl_xor(v, d, 64);
-      if ((threadIdx.x & 63) == 0) red[w][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < kEmTotal) {
-      const int k = threadIdx.x;
-      o.partial[(uint64_t)k * gridDim.x + blockIdx.x] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
+    block_partials<kEmTotal>([&](int k) {
+      const double v = k == 0 ? (double)n_trans : k == 1 ? (double)c.n_meas : k == 2 ? 1.0 : c.get(k - 3);
+      return (k == 2 ? live && bad : in) ? v : 0.0;
+    }, red, o.partial);
   }
 }
 

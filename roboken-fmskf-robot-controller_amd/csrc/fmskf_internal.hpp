@@ -468,6 +468,9 @@ int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool lib
 // state only (no FMSKF_CFG_COMP_POS), no fused ensemble record
 int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,
                     bool pred, hipStream_t st);
+// The window calls.  Their kernels share the table staging (kf6_lane.hpp stage_table), the
+// filtered state of a tick from its prior (smooth_lane.hpp smooth_filtered) and, for the calls that
+// return sums, the per-robot store, the block tree and the fold of the fleet total (window_lane.hpp).
 // the two passes of fmskf_tick_many_smooth (kernels_smooth.hip): the ticks of launch_kf6's
 // tick_many with the history store (plain ungated KF6 state only), then the backward recursion
 int launch_kf6_smooth_fwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,

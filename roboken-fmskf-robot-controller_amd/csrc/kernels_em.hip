@@ -12,28 +12,14 @@
 // read again with FMSKF_EM_ACCUMULATE.
 //
 // The fleet total is deterministic: every block reduces its lanes' fp64 values in a fixed tree
-// and writes one partial per quantity (em_store); k_em_fold, one block, adds the partials in
-// block order.  No floating-point atomics.
+// and writes one partial per quantity (em_store); k_window_fold (window_lane.hpp), one block, adds
+// the partials in block order.  No floating-point atomics.
 #include "em_lane.hpp"
 
 #pragma clang fp contract(off)
 
 namespace fmskf {
 
-// the block's copy of the sine table (kernels_kf6.hip stage_table)
-template <bool LIBM>
-__device__ __forceinline__ void em_stage_table(float *stab, const float *g) {
-  if (!LIBM) {
-    const int t = threadIdx.x;
-    const float a = g[t], b = g[t + kBlock];
-    const float c = t == 0 ? g[2 * kBlock] : 0.f;
-    stab[t] = a;
-    stab[t + kBlock] = b;
-    if (t == 0) stab[2 * kBlock] = c;
-    __syncthreads();
-  }
-}
-static_assert(2 * kBlock + 1 == 513, "table staging assumes 256-thread blocks");
 static_assert(kEmLds * kBlock * sizeof(double) + 513 * sizeof(float) + (kBlock / 64) * kEmTotal * sizeof(double) <= 65536,
               "accumulator columns, sine table and reduction buffer: 64 KiB of static LDS");
 
@@ -48,12 +34,7 @@ __device__ __forceinline__ void em_finish(const EmArgs &a, const float *stab, co
   for (int k = 0; k < 6; k++) xf[k] = x[k];
 #pragma unroll
   for (int k = 0; k < 21; k++) Pf[k] = P[k];
-  const bool meas = !O::VALID || m.valid;
-  if (meas) {
-    float y[4];
-    kf6_innov<O::LIBM>(m, stab, xf, y);
-    kf_update<MdKF6>(xf, Pf, y, a.prm.r);
-  }
+  const bool meas = smooth_filtered<O>(a.prm, stab, m, xf, Pf);
   c.finish(xf, e);
   if (meas) acc.template measured<O::LIBM>(m, stab, c);
 }
@@ -79,7 +60,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   hist_load(a.h, T - 1, ic, xa, Pa);
   ma = kf6_load_in<O>(a.in, n, T - 1, ic);
   acc.init(cols);
-  em_stage_table<O::LIBM>(stab, a.in.sintab);
+  stage_table<O::LIBM>(stab, a.in.sintab);
   if (T >= 2) {
     hist_load(a.h, T - 2, ic, xb, Pb);
     mb = kf6_load_in<O>(a.in, n, T - 2, ic);
@@ -90,12 +71,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
     for (int k = 0; k < 6; k++) xf[k] = xa[k];
 #pragma unroll
     for (int k = 0; k < 21; k++) Pf[k] = Pa[k];
-    const bool meas = !O::VALID || ma.valid;
-    if (meas) {
-      float y[4];
-      kf6_innov<O::LIBM>(ma, stab, xf, y);
-      kf_update<MdKF6>(xf, Pf, y, a.prm.r);
-    }
+    const bool meas = smooth_filtered<O>(a.prm, stab, ma, xf, Pf);
     c.start(xf, Pf);
     if (meas) acc.template measured<O::LIBM>(ma, stab, c);
   }
@@ -119,29 +95,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) 
   em_store(a.o, n, ic, live, T - 1, acc, red);
 }
 
-// total[k] = (old +) the nb block partials of quantity k added in block order, k < 34: the block
-// stages kEmFoldChunk partials of each quantity in LDS (coalesced loads), thread k adds its row in
-// order
-constexpr uint32_t kEmFoldChunk = 128;
-__global__ __launch_bounds__(kBlock) void k_em_fold(const double *partial, uint32_t nb, double *total,
-                                                    uint32_t accumulate) {
-  __shared__ double buf[kEmTotal][kEmFoldChunk];
-  double s = 0.0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += kEmFoldChunk) {
-    const uint32_t m = min(kEmFoldChunk, nb - b0);
-    for (uint32_t idx = threadIdx.x; idx < kEmTotal * kEmFoldChunk; idx += kBlock) {
-      const uint32_t k = idx / kEmFoldChunk, j = idx % kEmFoldChunk;
-      if (j < m) buf[k][j] = partial[(uint64_t)k * nb + b0 + j];
-    }
-    __syncthreads();
-    if (threadIdx.x < kEmTotal) {
-      for (uint32_t j = 0; j < m; j++) s = s + buf[threadIdx.x][j];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < kEmTotal) total[threadIdx.x] = accumulate ? total[threadIdx.x] + s : s;
-}
-
 int launch_kf6_em_bwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,
                       const EmOut &out, double *total, hipStream_t st) {
   if (p.lo || in.ens_blocks || in.fold_blocks || in.n_ticks == 0 || !hist.x || !hist.P || out.pitch < s.n ||
@@ -154,7 +107,7 @@ int launch_kf6_em_bwd(const DevState &s, const TickIn &in, const Kf6Params &p, b
   }, libm, in.valid != nullptr, in.rec != nullptr);
   int e = (int)hipGetLastError();
   if (e || !total) return e;
-  k_em_fold<<<1, kBlock, 0, st>>>(out.partial, g.x, total, out.accumulate);
+  k_window_fold<kEmTotal, 128><<<1, kBlock, 0, st>>>(out.partial, g.x, total, out.accumulate);
   return (int)hipGetLastError();
 }
 

@@ -39,22 +39,6 @@
 
 namespace fmskf {
 
-// copy the sine table to LDS: all global loads first, then the LDS writes, one barrier
-template <bool LIBM>
-__device__ __forceinline__ void stage_table(float *stab, const float *g) {
-  if (!LIBM) {
-    const int t = threadIdx.x;
-    const float a = g[t], b = g[t + kBlock];
-    const float c = t == 0 ? g[2 * kBlock] : 0.f;
-    stab[t] = a;
-    stab[t + kBlock] = b;
-    if (t == 0) stab[2 * kBlock] = c;
-    __syncthreads();
-  }
-}
-static_assert(2 * kBlock + 1 == 513, "table staging assumes 256-thread blocks");
-
-
 // tick_many: T ticks per launch, state in VGPRs throughout; the inputs of the next tick are
 // loaded while the current one computes.  Unrolled by two with ping-pong input registers
 // (ma / mb) so no input record is copied around the loop; clamped index, no live branch.

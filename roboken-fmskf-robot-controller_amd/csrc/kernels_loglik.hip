@@ -14,28 +14,13 @@
 // FMSKF_LL_ACCUMULATE.
 //
 // The fleet total is deterministic: every block reduces its lanes' fp64 values in a fixed tree
-// and writes one partial per quantity (loglik_store); k_loglik_fold, one block, adds the partials
-// in block order.  No floating-point atomics.
+// and writes one partial per quantity (loglik_store); k_window_fold (window_lane.hpp), one block,
+// adds the partials in block order.  No floating-point atomics.
 #include "loglik_lane.hpp"
 
 #pragma clang fp contract(off)
 
 namespace fmskf {
-
-// the block's copy of the sine table (kernels_kf6.hip stage_table)
-template <bool LIBM>
-__device__ __forceinline__ void loglik_stage_table(float *stab, const float *g) {
-  if (!LIBM) {
-    const int t = threadIdx.x;
-    const float a = g[t], b = g[t + kBlock];
-    const float c = t == 0 ? g[2 * kBlock] : 0.f;
-    stab[t] = a;
-    stab[t + kBlock] = b;
-    if (t == 0) stab[2 * kBlock] = c;
-    __syncthreads();
-  }
-}
-static_assert(2 * kBlock + 1 == 513, "table staging assumes 256-thread blocks");
 
 // waves_per_eu as k_kf6 has it.  The compiler's report (tools/resource_usage.py; the whole table and
 // k_kf6's own figures are in DESIGN.md section 3 and profiles/loglik.json), no scratch anywhere:
@@ -59,7 +44,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOM && O
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
   const auto old = kf6_keep_old<kf6_mask<O>()>(P);
   ma = kf6_load_in<O>(a.in, n, 0, ic);
-  loglik_stage_table<O::LIBM>(stab, a.in.sintab);
+  stage_table<O::LIBM>(stab, a.in.sintab);
   for (uint32_t t = 0; t < T; t += 2) {
     if (t + 1 < T) mb = kf6_load_in<O>(a.in, n, t + 1, ic);
     loglik_tick1<O>(ma, stab, a.prm, x, P, acc);
@@ -70,27 +55,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOM && O
   if (live) kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
   nan_guard(x, P, a.counters, live);
   loglik_store<MOM>(aa.o, n, ic, live, acc, red);
-}
-
-// total[k] = (old +) the nb block partials of quantity k added in block order: the block stages
-// kBlock partials of each quantity in LDS (coalesced loads), thread k adds its row in order
-__global__ __launch_bounds__(kBlock) void k_loglik_fold(const double *partial, uint32_t nb, double *total,
-                                                        uint32_t accumulate) {
-  __shared__ double buf[4][kBlock];
-  double s = 0.0;
-  for (uint32_t b0 = 0; b0 < nb; b0 += kBlock) {
-    const uint32_t b = b0 + threadIdx.x, m = min((uint32_t)kBlock, nb - b0);
-    if (b < nb) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) buf[k][threadIdx.x] = partial[(uint64_t)k * nb + b];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      for (uint32_t j = 0; j < m; j++) s = s + buf[threadIdx.x][j];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) total[threadIdx.x] = accumulate ? total[threadIdx.x] + s : s;
 }
 
 int launch_kf6_loglik(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const LoglikOut &out,
@@ -104,7 +68,7 @@ int launch_kf6_loglik(const DevState &s, const TickIn &in, const Kf6Params &p, b
   }, libm, in.valid != nullptr, in.rec != nullptr, out.innov_sum != nullptr || out.innov_outer != nullptr);
   int e = (int)hipGetLastError();
   if (e || !total) return e;
-  k_loglik_fold<<<1, kBlock, 0, st>>>(out.partial, g.x, total, out.accumulate);
+  k_window_fold<4, kBlock><<<1, kBlock, 0, st>>>(out.partial, g.x, total, out.accumulate);
   return (int)hipGetLastError();
 }
 

@@ -24,21 +24,6 @@
 
 namespace fmskf {
 
-// the block's copy of the sine table (kernels_kf6.hip stage_table)
-template <bool LIBM>
-__device__ __forceinline__ void smooth_stage_table(float *stab, const float *g) {
-  if (!LIBM) {
-    const int t = threadIdx.x;
-    const float a = g[t], b = g[t + kBlock];
-    const float c = t == 0 ? g[2 * kBlock] : 0.f;
-    stab[t] = a;
-    stab[t + kBlock] = b;
-    if (t == 0) stab[2 * kBlock] = c;
-    __syncthreads();
-  }
-}
-static_assert(2 * kBlock + 1 == 513, "table staging assumes 256-thread blocks");
-
 template <class O>
 __global__ __launch_bounds__(kBlock) void k_kf6_smooth_fwd(SmoothFwdArgs aa) {
   const Kf6Args &a = aa.k;
@@ -55,7 +40,7 @@ __global__ __launch_bounds__(kBlock) void k_kf6_smooth_fwd(SmoothFwdArgs aa) {
   kf6_load_state<O>(a.x, a.P, a.pitch, ic, x, P);
   const auto old = kf6_keep_old<kf6_mask<O>()>(P);
   ma = kf6_load_in<O>(a.in, n, 0, ic);
-  smooth_stage_table<O::LIBM>(stab, a.in.sintab);
+  stage_table<O::LIBM>(stab, a.in.sintab);
   for (uint32_t t = 0; t < T; t += 2) {
     if (t + 1 < T) mb = kf6_load_in<O>(a.in, n, t + 1, ic);
     hist_store(aa.h, t, ic, live, x, P);
@@ -67,17 +52,6 @@ __global__ __launch_bounds__(kBlock) void k_kf6_smooth_fwd(SmoothFwdArgs aa) {
   }
   if (live) kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
   nan_guard(x, P, a.counters, live);
-}
-
-// the filtered state of a tick from its prior (x, P) and inputs: the forward update itself
-template <class O>
-__device__ __forceinline__ void smooth_filtered(const SmoothBwdArgs &a, const float *stab, const Kf6In &m,
-                                                float (&x)[6], float (&P)[21]) {
-  if (!O::VALID || m.valid) {
-    float y[4];
-    kf6_innov<O::LIBM>(m, stab, x, y);
-    kf_update<MdKF6>(x, P, y, a.prm.r);
-  }
 }
 
 struct SmoothLane {
@@ -103,7 +77,7 @@ __device__ __forceinline__ void smooth_finish(const SmoothBwdArgs &a, const floa
   for (int k = 0; k < 6; k++) xf[k] = x[k];
 #pragma unroll
   for (int k = 0; k < 21; k++) Pf[k] = P[k];
-  smooth_filtered<O>(a, stab, m, xf, Pf);
+  smooth_filtered<O>(a.prm, stab, m, xf, Pf);
   c.finish(xf, e);
   smooth_out<WP>(a, t, ln, c);
 }
@@ -123,7 +97,7 @@ __global__ __launch_bounds__(kBlock) void k_kf6_smooth_bwd(SmoothBwdArgs a) {
   SmoothCarry<WP> c;
   hist_load(a.h, T - 1, ic, xa, Pa);
   ma = kf6_load_in<O>(a.in, n, T - 1, ic);
-  smooth_stage_table<O::LIBM>(stab, a.in.sintab);
+  stage_table<O::LIBM>(stab, a.in.sintab);
   if (T >= 2) {
     hist_load(a.h, T - 2, ic, xb, Pb);
     mb = kf6_load_in<O>(a.in, n, T - 2, ic);
@@ -134,7 +108,7 @@ __global__ __launch_bounds__(kBlock) void k_kf6_smooth_bwd(SmoothBwdArgs a) {
     for (int k = 0; k < 6; k++) xf[k] = xa[k];
 #pragma unroll
     for (int k = 0; k < 21; k++) Pf[k] = Pa[k];
-    smooth_filtered<O>(a, stab, ma, xf, Pf);
+    smooth_filtered<O>(a.prm, stab, ma, xf, Pf);
     c.start(xf, Pf);
     smooth_out<WP>(a, T - 1, ln, c);
   }

@@ -288,6 +288,21 @@ struct Kf6Gate<O, true> {
 template <class O, class A>
 using Kf6GateOf = Kf6Gate<O, std::is_same<A, GateArgs>::value>;
 
+// copy the sine table to the block's LDS: all global loads first, then the LDS writes, one barrier
+template <bool LIBM>
+__device__ __forceinline__ void stage_table(float *stab, const float *g) {
+  if (!LIBM) {
+    const int t = threadIdx.x;
+    const float a = g[t], b = g[t + kBlock];
+    const float c = t == 0 ? g[2 * kBlock] : 0.f;
+    stab[t] = a;
+    stab[t + kBlock] = b;
+    if (t == 0) stab[2 * kBlock] = c;
+    __syncthreads();
+  }
+}
+static_assert(2 * kBlock + 1 == 513, "table staging assumes 256-thread blocks");
+
 // z = (deg2rad(yaw), -deg2rad(gz), wheel velocity rotated by the measured heading)
 // (imu_task_main.cpp:102-104, util_mymath.hpp:16, imu_if_wt901c.cpp:113,
 //  VD_vehicle_controller.cpp:21-33,47-51); y = z - H x with the heading innovation wrapped

@@ -20,7 +20,7 @@
 //
 // tests/loglik_ref.py restates the scheme in numpy.
 #pragma once
-#include "kf6_lane.hpp"
+#include "window_lane.hpp"
 
 #pragma clang fp contract(off)
 
@@ -106,19 +106,9 @@ __device__ __forceinline__ void loglik_tick1(const Kf6In &m, const float *tab, c
   kf_predict_cov<MdKF6>(P, [&](int, int) { return dt; }, prm.q);
 }
 
-// one value of a plain [N] plane (or of a row of the innovation planes) at the lane's slot of its
-// 256-robot chunk: overwritten, or with FMSKF_LL_ACCUMULATE old + new
-template <typename T>
-__device__ __forceinline__ void loglik_put(T *plane, uint32_t hb, uint64_t n, uint32_t li, bool acc, T v) {
-  if (acc) v = ld_chunk<T, 0>(plane, hb, n, li) + v;
-  st_chunk<T, st_pol(0)>(plane, hb, n, li, v);
-}
-
 // The stores after the last tick (ic: the lane's clamped robot, its chunk wave-uniform), then the
-// block's partial totals: the lanes' fp64 values (zeros for a dead lane and for a robot left out,
-// which counts in [3]) through a fixed butterfly inside each wave -- every lane ends with the
-// same sum, since a + b is b + a -- and the four waves' sums added in wave order, one thread per
-// quantity.  red: [wave][quantity].
+// block's partial totals (window_lane.hpp block_partials) of the lanes' fp64 values: zeros for a
+// dead lane and for a robot left out, which counts in [3].  red: [wave][quantity].
 template <bool MOM>
 __device__ __forceinline__ void loglik_store(const LoglikOut &o, uint64_t n, uint32_t ic, bool live,
                                              const LoglikAcc<MOM> &c, double (*red)[4]) {
@@ -126,40 +116,27 @@ __device__ __forceinline__ void loglik_store(const LoglikOut &o, uint64_t n, uin
   const bool acc = o.accumulate != 0;
   const double nis = c.nis_sum(), ld = c.logdet_sum();
   if (live) {
-    if (o.n_meas) loglik_put<uint32_t>(o.n_meas, hb, n, li, acc, c.n);
-    if (o.nis_sum) loglik_put<double>(o.nis_sum, hb, n, li, acc, nis);
-    if (o.logdet_sum) loglik_put<double>(o.logdet_sum, hb, n, li, acc, ld);
+    if (o.n_meas) window_put<uint32_t>(o.n_meas, hb, n, li, acc, c.n);
+    if (o.nis_sum) window_put<double>(o.nis_sum, hb, n, li, acc, nis);
+    if (o.logdet_sum) window_put<double>(o.logdet_sum, hb, n, li, acc, ld);
     if constexpr (MOM) {
       if (o.innov_sum) {
 #pragma unroll
         for (int a = 0; a < 4; a++)
-          loglik_put<double>(o.innov_sum + (uint64_t)a * o.pitch, hb, n, li, acc, (double)c.s_hi[a] + (double)c.s_lo[a]);
+          window_put<double>(o.innov_sum + (uint64_t)a * o.pitch, hb, n, li, acc, (double)c.s_hi[a] + (double)c.s_lo[a]);
       }
       if (o.innov_outer) {
 #pragma unroll
         for (int k = 0; k < 10; k++)
-          loglik_put<double>(o.innov_outer + (uint64_t)k * o.pitch, hb, n, li, acc,
+          window_put<double>(o.innov_outer + (uint64_t)k * o.pitch, hb, n, li, acc,
                              (double)c.o_hi[k] + (double)c.o_lo[k]);
       }
     }
   }
   if (o.partial) {
     const bool in = live && !c.bad;
-    double v[4] = {in ? (double)c.n : 0.0, in ? nis : 0.0, in ? ld : 0.0, live && c.bad ? 1.0 : 0.0};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) v[k] = v[k] + __shfl_xor(v[k], d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) red[threadIdx.x >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-      const int k = threadIdx.x;
-      o.partial[(uint64_t)k * gridDim.x + blockIdx.x] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
-    }
+    const double v[4] = {in ? (double)c.n : 0.0, in ? nis : 0.0, in ? ld : 0.0, live && c.bad ? 1.0 : 0.0};
+    block_partials<4>([&](int k) { return v[k]; }, red, o.partial);
   }
 }
 

@@ -267,4 +267,20 @@ struct SmoothCarry {
   }
 };
 
+// The filtered state of a tick from a copy of its prior (x, P) and its inputs, in place: the
+// forward update itself (kf6_innov, kf_update: the forward pass's bits).  Returns whether the tick
+// was measured.  The callers copy the prior themselves, since they keep it for the next tick down
+// ("What the window calls share", on why the copy is not made in here).
+template <class O>
+__device__ __forceinline__ bool smooth_filtered(const Kf6Params &prm, const float *stab, const Kf6In &m,
+                                                float (&xf)[6], float (&Pf)[21]) {
+  const bool meas = !O::VALID || m.valid;
+  if (meas) {
+    float y[4];
+    kf6_innov<O::LIBM>(m, stab, xf, y);
+    kf_update<MdKF6>(xf, Pf, y, prm.r);
+  }
+  return meas;
+}
+
 }  // namespace fmskf

@@ -668,6 +668,49 @@ class Engine:
         grows); 0 frees it"""
         check(load().fmskf_smooth_reserve(self.h, int(n_ticks)), "smooth_reserve")
 
+    def _window_out(self, call, shapes, planes, st, flag, names, accumulate_into, keep):
+        """The output dict of tick_many_loglik / tick_many_em and its ctypes struct `st`, filled: new
+        arrays for `names` in the memory of the inputs (keep), or the caller's accumulate_into
+        (validated; `flag` set).  shapes: every key the call knows; planes: its multi-row keys, which
+        share one row pitch >= N."""
+        if accumulate_into is None:
+            if keep.mem == MEM_DEVICE:
+                import torch
+                dev = keep.keep[0].device
+                mk = lambda k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_meas" else torch.float64, device=dev)
+            else:
+                mk = lambda k: np.empty(shapes[k], np.uint32 if k == "n_meas" else np.float64)
+            out = {k: mk(k) for k in names}
+        else:
+            out = accumulate_into
+            st.flags = flag
+            if not out or set(out) - set(shapes):
+                raise ValueError(f"{call}: accumulate_into needs some of {sorted(shapes)} and nothing else")
+        tor = [_is_torch(v) for v in out.values()]
+        if any(tor) != all(tor):
+            raise ValueError(f"{call}: the outputs must live in the same memory")
+        cols = {int(out[k].shape[-1]) for k in planes if k in out and len(out[k].shape) == 2}
+        if len(cols) > 1 or (cols and min(cols) < self.n):
+            raise ValueError(f"{call}: {' and '.join(planes)} need one row pitch >= N")
+        pitch = cols.pop() if cols else self.n
+        for k, v in out.items():
+            want = shapes[k] if len(shapes[k]) == 1 else (shapes[k][0], pitch)
+            if tuple(v.shape) != want:
+                raise ValueError(f"{call}: {k} has shape {tuple(v.shape)}, want {want}")
+            if tor[0]:
+                dt = "torch.float64" if k != "n_meas" else None
+                if not v.is_cuda or not v.is_contiguous() or (str(v.dtype) != dt if dt else v.element_size() != 4):
+                    raise TypeError(f"{call}: a torch {k} must be a contiguous device tensor of "
+                                    f"{'float64' if dt else 'int32'}")
+            elif not isinstance(v, np.ndarray) or v.dtype != (np.uint32 if k == "n_meas" else np.float64) \
+                    or not v.flags.c_contiguous or not v.flags.writeable:
+                raise TypeError(f"{call}: a host {k} must be a writable C-contiguous numpy array of "
+                                f"{'uint32' if k == 'n_meas' else 'float64'}")
+            setattr(st, k, v.data_ptr() if tor[0] else v.ctypes.data)
+        st.mem = MEM_DEVICE if tor[0] else MEM_HOST
+        st.pitch = 0 if pitch == self.n else pitch
+        return out, st
+
     def tick_many_loglik(self, n_ticks, tick_stride=None, moments=False, total=False, accumulate_into=None, **kw):
         """fmskf_tick_many_loglik (KF6): the ticks of tick_many, plus the window's innovation sums
         per robot.  Returns a dict: n_meas [N] uint32, nis_sum [N] and logdet_sum [N] float64 (what
@@ -684,45 +727,10 @@ class Engine:
         ti, keep = self._inputs(kw, T, stride)
         shapes = {"n_meas": (self.n,), "nis_sum": (self.n,), "logdet_sum": (self.n,), "innov_sum": (4, self.n),
                   "innov_outer": (10, self.n), "total": (4,)}
-        lo = _lib.LoglikOut()
-        if accumulate_into is None:
-            names = ["n_meas", "nis_sum", "logdet_sum"] + (["innov_sum", "innov_outer"] if moments else []) + \
-                (["total"] if total else [])
-            if keep.mem == MEM_DEVICE:
-                import torch
-                dev = keep.keep[0].device
-                mk = lambda k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_meas" else torch.float64, device=dev)
-            else:
-                mk = lambda k: np.empty(shapes[k], np.uint32 if k == "n_meas" else np.float64)
-            out = {k: mk(k) for k in names}
-        else:
-            out = accumulate_into
-            lo.flags = _lib.LL_ACCUMULATE
-            if not out or set(out) - set(shapes):
-                raise ValueError(f"tick_many_loglik: accumulate_into needs some of {sorted(shapes)} and nothing else")
-        tor = [_is_torch(v) for v in out.values()]
-        if any(tor) != all(tor):
-            raise ValueError("tick_many_loglik: the outputs must live in the same memory")
-        cols = {int(out[k].shape[-1]) for k in ("innov_sum", "innov_outer") if k in out and len(out[k].shape) == 2}
-        if len(cols) > 1 or (cols and min(cols) < self.n):
-            raise ValueError("tick_many_loglik: innov_sum and innov_outer need one row pitch >= N")
-        pitch = cols.pop() if cols else self.n
-        for k, v in out.items():
-            want = shapes[k] if len(shapes[k]) == 1 else (shapes[k][0], pitch)
-            if tuple(v.shape) != want:
-                raise ValueError(f"tick_many_loglik: {k} has shape {tuple(v.shape)}, want {want}")
-            if tor[0]:
-                dt = "torch.float64" if k != "n_meas" else None
-                if not v.is_cuda or not v.is_contiguous() or (str(v.dtype) != dt if dt else v.element_size() != 4):
-                    raise TypeError(f"tick_many_loglik: a torch {k} must be a contiguous device tensor of "
-                                    f"{'float64' if dt else 'int32'}")
-            elif not isinstance(v, np.ndarray) or v.dtype != (np.uint32 if k == "n_meas" else np.float64) \
-                    or not v.flags.c_contiguous or not v.flags.writeable:
-                raise TypeError(f"tick_many_loglik: a host {k} must be a writable C-contiguous numpy array of "
-                                f"{'uint32' if k == 'n_meas' else 'float64'}")
-            setattr(lo, k, v.data_ptr() if tor[0] else v.ctypes.data)
-        lo.mem = MEM_DEVICE if tor[0] else MEM_HOST
-        lo.pitch = 0 if pitch == self.n else pitch
+        names = ["n_meas", "nis_sum", "logdet_sum"] + (["innov_sum", "innov_outer"] if moments else []) + \
+            (["total"] if total else [])
+        out, lo = self._window_out("tick_many_loglik", shapes, ("innov_sum", "innov_outer"), _lib.LoglikOut(),
+                                   _lib.LL_ACCUMULATE, names, accumulate_into, keep)
         check(load().fmskf_tick_many_loglik(self.h, C.byref(ti), T, stride, C.byref(lo)), "tick_many_loglik")
         return out
 
@@ -742,46 +750,11 @@ class Engine:
         stride = self.n if tick_stride is None else int(tick_stride)
         ti, keep = self._inputs(kw, T, stride)
         shapes = {"n_meas": (self.n,), "sq": (21, self.n), "sr": (10, self.n), "total": (_lib.EM_TOTAL_LEN,)}
-        eo = _lib.EmOut()
-        if accumulate_into is None:
-            names = (["n_meas", "sq", "sr"] if per_robot else []) + (["total"] if total else [])
-            if not names:
-                raise ValueError("tick_many_em: neither per_robot nor total")
-            if keep.mem == MEM_DEVICE:
-                import torch
-                dev = keep.keep[0].device
-                mk = lambda k: torch.empty(shapes[k], dtype=torch.int32 if k == "n_meas" else torch.float64, device=dev)
-            else:
-                mk = lambda k: np.empty(shapes[k], np.uint32 if k == "n_meas" else np.float64)
-            out = {k: mk(k) for k in names}
-        else:
-            out = accumulate_into
-            eo.flags = _lib.EM_ACCUMULATE
-            if not out or set(out) - set(shapes):
-                raise ValueError(f"tick_many_em: accumulate_into needs some of {sorted(shapes)} and nothing else")
-        tor = [_is_torch(v) for v in out.values()]
-        if any(tor) != all(tor):
-            raise ValueError("tick_many_em: the outputs must live in the same memory")
-        cols = {int(out[k].shape[-1]) for k in ("sq", "sr") if k in out and len(out[k].shape) == 2}
-        if len(cols) > 1 or (cols and min(cols) < self.n):
-            raise ValueError("tick_many_em: sq and sr need one row pitch >= N")
-        pitch = cols.pop() if cols else self.n
-        for k, v in out.items():
-            want = shapes[k] if len(shapes[k]) == 1 else (shapes[k][0], pitch)
-            if tuple(v.shape) != want:
-                raise ValueError(f"tick_many_em: {k} has shape {tuple(v.shape)}, want {want}")
-            if tor[0]:
-                dt = "torch.float64" if k != "n_meas" else None
-                if not v.is_cuda or not v.is_contiguous() or (str(v.dtype) != dt if dt else v.element_size() != 4):
-                    raise TypeError(f"tick_many_em: a torch {k} must be a contiguous device tensor of "
-                                    f"{'float64' if dt else 'int32'}")
-            elif not isinstance(v, np.ndarray) or v.dtype != (np.uint32 if k == "n_meas" else np.float64) \
-                    or not v.flags.c_contiguous or not v.flags.writeable:
-                raise TypeError(f"tick_many_em: a host {k} must be a writable C-contiguous numpy array of "
-                                f"{'uint32' if k == 'n_meas' else 'float64'}")
-            setattr(eo, k, v.data_ptr() if tor[0] else v.ctypes.data)
-        eo.mem = MEM_DEVICE if tor[0] else MEM_HOST
-        eo.pitch = 0 if pitch == self.n else pitch
+        names = (["n_meas", "sq", "sr"] if per_robot else []) + (["total"] if total else [])
+        if accumulate_into is None and not names:
+            raise ValueError("tick_many_em: neither per_robot nor total")
+        out, eo = self._window_out("tick_many_em", shapes, ("sq", "sr"), _lib.EmOut(), _lib.EM_ACCUMULATE, names,
+                                   accumulate_into, keep)
         check(load().fmskf_tick_many_em(self.h, C.byref(ti), T, stride, C.byref(eo)), "tick_many_em")
         return out
 

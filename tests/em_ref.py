@@ -222,7 +222,7 @@ def bounds(dev32, ref):
 
 def fleet_fold(d, Tn):
     """total [34] of a per-robot result (n_meas [N], sq [21, N], sr [10, N]) of a window of Tn
-    ticks: the kernels' fixed tree (csrc/em_lane.hpp em_store, kernels_em.hip k_em_fold), which is
+    ticks: the kernels' fixed tree (csrc/em_lane.hpp em_store, window_lane.hpp k_window_fold), which is
     loglik_ref.fleet_fold's, over each of the 34 rows {n_trans, n_meas, left out, sq, sr}, the
     robots left out (a NaN in their sums) as zeros in every row but the third -- the same bits."""
     sq, sr_ = np.asarray(d["sq"], np.float64), np.asarray(d["sr"], np.float64)

@@ -265,8 +265,8 @@ def same(a, b, what):
 
 
 def fleet_fold(v):
-    """The kernels' fixed tree over a per-robot float64 array (csrc/loglik_lane.hpp loglik_store,
-    kernels_loglik.hip k_loglik_fold): zeros for the lanes past N, inside every 64-lane wave the
+    """The kernels' fixed tree over a per-robot float64 array (csrc/window_lane.hpp block_partials,
+    k_window_fold): zeros for the lanes past N, inside every 64-lane wave the
     butterfly v[i] + v[i ^ d] for d = 1, 2, .. 32, the four waves of a 256-robot block added in
     order, the blocks added in order from 0.0 -- every addition an IEEE one, so the same bits."""
     v = np.asarray(v, np.float64)

@@ -162,6 +162,7 @@ def test_total_is_deterministic_and_close(w):
     for k, name in enumerate(LIK):
         v = a[name].astype(np.float64)
         assert abs(a["total"][k] - math.fsum(v)) <= N * 2.0 ** -52 * math.fsum(np.abs(v)), name
+        assert a["total"][k] == lr.fleet_fold(a[name]), f"{name}: the total is not the fixed tree of the per-robot sums"
     assert a["total"][0] == int(a["n_meas"].sum()) and a["total"][3] == 0
 
 
