@@ -231,7 +231,8 @@ int fmskf_tick_many(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_tick
  * fmskf_last_kernel_ms cover both passes.
  *
  * FMSKF_ENOTSUP: a model other than KF6, a handle with FMSKF_CFG_COMP_POS, a handle with a gate
- * set (the accept / force decisions would have to be recorded per tick).  FMSKF_EINVAL: out or
+ * set (its accept / force decisions are recorded per tick by fmskf_tick_many_trace, whose
+ * `applied` plane lets an ungated handle replay the gated trajectory).  FMSKF_EINVAL: out or
  * out->x NULL, reserved != 0, a bad mem flag, pitch non-zero and below N, n_ticks == 0,
  * everything fmskf_tick_many refuses, a call inside a graph capture.  Each is raised before
  * anything is launched, and the handle is untouched.  FMSKF_ENOMEM: the workspace or the output
@@ -395,6 +396,67 @@ typedef struct fmskf_em_out {
 int fmskf_tick_many_em(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
                        uint64_t tick_stride, const fmskf_em_out *out);
 int fmskf_em_mstep(const double *total, double *q /*[21]*/, double *r /*[10]*/);
+
+/* ---- per-tick trace of a replayed window (KF6, gated or not) ------------------- */
+/* The calls above return the end of a window or a sum over it.  This one returns what the filter
+ * did at every tick: the NIS time series (the standard consistency diagnostic: when did a robot
+ * start slipping?), the gate's decision of every tick, and the filtered trajectory, decimated if
+ * wanted -- in one launch instead of T single ticks each followed by a readout of the fleet.
+ *
+ * fmskf_tick_many_trace takes the inputs of fmskf_tick_many (records or the three planes, an
+ * optional `valid` mask, host or device memory; explicit planes required).  KF6 without
+ * FMSKF_CFG_COMP_POS, with or without a gate (fmskf_set_gate, below).
+ * 1. It advances the handle exactly as fmskf_tick_many(h, in, n_ticks, tick_stride) would: x, P
+ *    and every counter are bit for bit what that call leaves (the non-finite guard counts in
+ *    counter [0] as that call's launch does), and on a gated handle the gate state too: status,
+ *    run, rejects and the last evaluated NIS.
+ * 2. Per tick t and robot, rows t of the three per-tick planes:
+ *    gated handle, robot measured at tick t (`valid` NULL or non-zero): status[t] the gate's
+ *      decision (FMSKF_GATE_ACCEPTED / REJECTED / FORCED), nis[t] the NIS the tick evaluated,
+ *      applied or not, applied[t] 1 for ACCEPTED or FORCED, else 0;
+ *    ungated handle, robot measured: status[t] = FMSKF_GATE_ACCEPTED, applied[t] = 1, nis[t] the
+ *      value a monitor-only gate (nis_max = +INFINITY, max_consecutive = 0) reports, bit for bit;
+ *    no measurement (valid == 0): status[t] = FMSKF_GATE_NONE, applied[t] = 0, nis[t] the quiet
+ *      NaN 0x7FC00000.
+ * 3. `applied` has the format of fmskf_tick_inputs.valid with tick_stride == pitch.  A rejected
+ *    update is the valid == 0 skip bit for bit and an applied or forced one the ungated update, so
+ *    an ungated handle of the same configuration, set to the state the gated handle had before the
+ *    window (fmskf_get_state / fmskf_set_state) and fed the same inputs with valid = applied,
+ *    repeats the gated trajectory exactly; fmskf_tick_many_smooth, fmskf_tick_many_loglik and
+ *    fmskf_tick_many_em, which refuse a gated handle, work on that one.
+ * 4. State rows: row j of x / P is the state after tick (j + 1) * every - 1, i.e. what
+ *    fmskf_get_state returns after (j + 1) * every ticks; n_ticks / every rows, rounded down.
+ * Only the declared rows and columns are written: columns [N, pitch) and memory past the last row
+ * are left alone.  Every output pointer is optional, but not all of them.  One launch;
+ * fmskf_set_timing / fmskf_last_kernel_ms record it as one entry.  Host outputs are mirrored on
+ * the device at the caller's pitch and copied out on the handle's stream; the call returns when
+ * they are complete.  Device outputs are asynchronous on the handle's stream; the float planes
+ * must be 4-byte aligned, the byte planes may have any alignment and any pitch.
+ * 16 B read and 4 + 1 + 1 B written per robot-tick, + 24 / every for x and 84 / every for P; the
+ * state is read and written once per launch.
+ *
+ * FMSKF_ENOTSUP: a model other than KF6, a handle with FMSKF_CFG_COMP_POS.  FMSKF_EINVAL: out
+ * NULL, every output pointer NULL, reserved or reserved2 non-zero, a bad mem flag, pitch non-zero
+ * and below N, n_ticks == 0, x or P given with every == 0 or every > n_ticks, a misaligned device
+ * float plane, everything fmskf_tick_many refuses, a call inside a graph capture.  FMSKF_ENOMEM:
+ * the host staging cannot be allocated.  Each is raised before anything is launched, and the
+ * handle's state is untouched. */
+typedef struct fmskf_trace_out {
+  uint32_t mem;        /* FMSKF_MEM_HOST or FMSKF_MEM_DEVICE for every pointer below */
+  uint32_t reserved;   /* must be 0 */
+  uint64_t pitch;      /* elements between consecutive rows of every plane; 0 = N, otherwise >= N */
+  uint32_t every;      /* read only when x or P is given: 1 .. n_ticks */
+  uint32_t reserved2;  /* must be 0 */
+  float   *nis;        /* [T][pitch]  NIS evaluated at tick t */
+  uint8_t *status;     /* [T][pitch]  FMSKF_GATE_NONE / ACCEPTED / REJECTED / FORCED of tick t */
+  uint8_t *applied;    /* [T][pitch]  1 where tick t's update was applied, else 0: the format of
+                          fmskf_tick_inputs.valid with tick_stride == pitch */
+  float   *x;          /* [T/every][6][pitch]  state after ticks every, 2*every, ... */
+  float   *P;          /* [T/every][21][pitch] packed like fmskf_get_state; NULL = not stored */
+} fmskf_trace_out;
+
+int fmskf_tick_many_trace(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_ticks,
+                          uint64_t tick_stride, const fmskf_trace_out *out);
 
 /* ---- chi-square innovation gate (KF6) ---------------------------------------- */
 /* Off by default: a handle that never sets a gate runs the kernels and computes the bits it

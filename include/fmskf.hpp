@@ -143,6 +143,15 @@ class Robots {
     check(fmskf_tick_many_em(h_, in, n_ticks, tick_stride, &out), "fmskf_tick_many_em");
   }
 
+  // a replayed window of T ticks with every tick's NIS, gate status and applied byte per robot, and
+  // the state after every out.every-th tick (fmskf_tick_many_trace: KF6 with or without a gate; the
+  // state, and a gate's, is left as fmskf_tick_many leaves it).  out.applied, fed as `valid` to an
+  // ungated handle set to the same start, replays a gated log through the three calls above
+  void tick_many_trace(const fmskf_tick_inputs *in, uint32_t n_ticks, uint64_t tick_stride,
+                       const fmskf_trace_out &out) {
+    check(fmskf_tick_many_trace(h_, in, n_ticks, tick_stride, &out), "fmskf_tick_many_trace");
+  }
+
   // the robots for which any criterion of prm holds (fmskf_select: a state gone non-finite, a
   // position covariance above a threshold, a gate that keeps rejecting), strictly ascending --
   // the list correct_pose and the subset calls take.  robots / reason [capacity] (reason may be

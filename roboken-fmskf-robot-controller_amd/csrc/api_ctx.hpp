@@ -12,7 +12,9 @@
 //   api_smooth.cpp      fmskf_tick_many_smooth and its workspace
 //   api_loglik.cpp      fmskf_tick_many_loglik
 //   api_em.cpp          fmskf_tick_many_em, fmskf_em_mstep
-// The three window calls share their front end, at the end of this header: the model check, the
+//   api_trace.cpp       fmskf_tick_many_trace
+// The window calls share their front end, at the end of this header: the model check (the trace,
+// which takes a gated handle, has its own), the
 // call opening (window_call), bytes_mul, ensure_partial, the staging of host outputs from a piece
 // table (window_pieces.hpp: the table and its plan, host only) and the bracketing of two passes.
 #pragma once
@@ -519,9 +521,11 @@ void ctrl_materialize(fmskf_ctx *h);
 // before the first launch -- a failure leaves the state as it was -- ens_flush, the launches.
 // ---------------------------------------------------------------------------
 
-// plain ungated KF6: a gate's accept / force decisions would have to be recorded per tick (and its
-// rejected ticks leave the sums), and the compensated positions have their own update and no
-// smoother.  what: "smoothing is", "the innovation log-likelihood is"
+// plain ungated KF6: a gate's accept / force decisions are recorded per tick by
+// fmskf_tick_many_trace (api_trace.cpp, which has its own model check), whose `applied` plane lets
+// an ungated handle replay the gated trajectory through these calls (a gate's rejected ticks
+// leave the sums), and the compensated positions have their own update and no smoother.
+// what: "smoothing is", "the innovation log-likelihood is"
 inline void check_window_model(const fmskf_ctx *h, const char *what) {
   const std::string w(what);
   if (h->cfg.model != FMSKF_MODEL_KF6) fail(FMSKF_ENOTSUP, w + " for KF6");

@@ -275,6 +275,17 @@ struct EmOut {
   double *partial;
   uint32_t accumulate;  // FMSKF_EM_ACCUMULATE: old + new instead of new
 };
+// fmskf_tick_many_trace (kernels_trace.hip; an argument struct of its own): the caller's outputs as
+// the kernel sees them (device pointers, any may be null).  pitch: elements between the rows of
+// every plane; every: a state row after every `every`-th tick (read only with x or P)
+struct TraceOut {
+  float *nis;        // [T][pitch]
+  uint8_t *status;   // [T][pitch]
+  uint8_t *applied;  // [T][pitch]
+  float *x, *P;      // [T / every][6][pitch], [T / every][21][pitch]
+  uint64_t pitch;
+  uint32_t every;
+};
 struct Ekf9Params {
   float dt;
   float q[45];
@@ -487,6 +498,11 @@ int launch_kf6_loglik(const DevState &s, const TickIn &in, const Kf6Params &p, b
 // blocks' partials into it
 int launch_kf6_em_bwd(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, const SmoothHist &hist,
                       const EmOut &out, double *total, hipStream_t st);
+// fmskf_tick_many_trace (kernels_trace.hip): the ticks of launch_kf6's tick_many, or with `gate` of
+// launch_kf6_gate's, with every tick's NIS, status and applied byte and the decimated state rows
+// stored as the loop goes (plain KF6 state only); one launch
+int launch_kf6_trace(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev *gate, bool libm,
+                     const TraceOut &out, hipStream_t st);
 // the gate words unpacked into status [N], run [N], rejects [N] (device pointers, any may be null)
 int launch_gate_unpack(const uint32_t *word, uint64_t n, uint8_t *status, uint8_t *run, uint32_t *rejects,
                        hipStream_t st);

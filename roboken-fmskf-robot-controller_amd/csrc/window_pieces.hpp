@@ -1,5 +1,5 @@
 // window_pieces.hpp -- the output arrays of a window call (fmskf_tick_many_loglik,
-// fmskf_tick_many_em) as a table of pieces, and the plan of their device mirror.  Host only,
+// fmskf_tick_many_em, fmskf_tick_many_trace) as a table of pieces, and the plan of their device mirror.  Host only,
 // nothing from HIP (tests/native/piece_table.cpp builds it with a plain C++ compiler); api_ctx.hpp
 // includes it and runs the copies.
 //
@@ -46,7 +46,7 @@ inline bool plan_pieces(Piece *pc, int count, uint64_t *bytes) {
   return true;
 }
 
-// the piece tables of the two calls: n robots, `pitch` elements between the rows of the multi-row
+// the piece tables of the calls: n robots, `pitch` elements between the rows of the multi-row
 // planes; a plain [N] plane and the total are one row
 inline void loglik_pieces(Piece (&pc)[6], uint64_t n, uint64_t pitch, void *n_meas, void *nis_sum, void *logdet_sum,
                           void *innov_sum, void *innov_outer, void *total) {
@@ -62,6 +62,16 @@ inline void em_pieces(Piece (&pc)[4], uint64_t n, uint64_t pitch, void *n_meas, 
   pc[1] = {sq, 8, 21, n, pitch};
   pc[2] = {sr, 8, 10, n, pitch};
   pc[3] = {total, 8, 1, 34, 34};  // FMSKF_EM_TOTAL_LEN
+}
+// fmskf_tick_many_trace: n_ticks rows of the three per-tick planes, `rows` (n_ticks / every) state
+// rows of 6 and 21 planes each, every row `pitch` elements from the next
+inline void trace_pieces(Piece (&pc)[5], uint64_t n, uint64_t pitch, uint64_t n_ticks, uint64_t rows, void *nis,
+                         void *status, void *applied, void *x, void *P) {
+  pc[0] = {nis, 4, n_ticks, n, pitch};
+  pc[1] = {status, 1, n_ticks, n, pitch};
+  pc[2] = {applied, 1, n_ticks, n, pitch};
+  pc[3] = {x, 4, 6 * rows, n, pitch};
+  pc[4] = {P, 4, 21 * rows, n, pitch};
 }
 
 }  // namespace fmskf

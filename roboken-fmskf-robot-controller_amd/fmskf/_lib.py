@@ -105,6 +105,13 @@ class EmOut(C.Structure):
                 ("sq", C.c_void_p), ("sr", C.c_void_p), ("total", C.c_void_p)]
 
 
+# fmskf_tick_many_trace
+class TraceOut(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("reserved", C.c_uint32), ("pitch", C.c_uint64), ("every", C.c_uint32),
+                ("reserved2", C.c_uint32), ("nis", C.c_void_p), ("status", C.c_void_p), ("applied", C.c_void_p),
+                ("x", C.c_void_p), ("P", C.c_void_p)]
+
+
 class Gate(C.Structure):
     _fields_ = [("nis_max", C.c_float), ("max_consecutive", C.c_uint32)]
 
@@ -186,6 +193,7 @@ SIGNATURES = {
     "fmskf_tick_many_loglik": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(LoglikOut)]),
     "fmskf_tick_many_em": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(EmOut)]),
     "fmskf_em_mstep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fmskf_tick_many_trace": (C.c_int, [_H, C.POINTER(TickInputs), C.c_uint32, C.c_uint64, C.POINTER(TraceOut)]),
     "fmskf_get_pose": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_vel": (C.c_int, [_H, _P, _P, _P, C.c_uint32]),
     "fmskf_get_state": (C.c_int, [_H, _P, _P, C.c_uint32]),

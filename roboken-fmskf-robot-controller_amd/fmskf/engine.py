@@ -758,6 +758,70 @@ class Engine:
         check(load().fmskf_tick_many_em(self.h, C.byref(ti), T, stride, C.byref(eo)), "tick_many_em")
         return out
 
+    def tick_many_trace(self, n_ticks, tick_stride=None, every=None, want_P=False, pitch=0, out=None, **kw):
+        """fmskf_tick_many_trace (KF6, with or without a gate): the ticks of tick_many, plus what the
+        filter did at every tick.  Returns a dict of the planes asked for: nis [T, C] float32 (the
+        quiet NaN 0x7FC00000 where the tick carried no measurement), status [T, C] uint8 (GATE_*),
+        applied [T, C] uint8 (1 where the update ran: the format of `valid` with tick_stride == C);
+        with `every` x [T // every, 6, C], the state after ticks every, 2 * every, ..., and with
+        want_P (every defaults to 1 then) P [T // every, 21, C] packed like get_state.  C = pitch,
+        or N; with pitch > N the elements past N of every row are left alone.  numpy inputs give
+        numpy results; torch device inputs give torch device results, asynchronous on the
+        handle's stream.
+        out: a dict of the caller's arrays instead (some of nis, status, applied, x, P; numpy, or
+        contiguous torch device tensors whatever the inputs' memory); its keys select the outputs,
+        an array may have more rows than the call writes, and those are left alone."""
+        T = int(n_ticks)
+        stride = self.n if tick_stride is None else int(tick_stride)
+        ti, keep = self._inputs(kw, T, stride)
+        cols = int(pitch) if pitch else self.n
+        if cols < self.n:
+            raise ValueError("tick_many_trace: pitch < N")
+        dts = {"nis": np.float32, "status": np.uint8, "applied": np.uint8, "x": np.float32, "P": np.float32}
+        if out is None:
+            if want_P and every is None:
+                every = 1
+            names = ["nis", "status", "applied"] + (["x"] if every is not None else []) + (["P"] if want_P else [])
+        else:
+            names = list(out)
+            if not names or set(names) - set(dts):
+                raise ValueError(f"tick_many_trace: out needs some of {sorted(dts)} and nothing else")
+            if every is None and ("x" in out or "P" in out):
+                every = 1
+        ev = 0 if every is None else int(every)
+        if ("x" in names or "P" in names) and not 1 <= ev <= T:
+            raise ValueError("tick_many_trace: every must be 1 .. n_ticks")
+        rows = T // ev if ev else 0
+        shapes = {"nis": (T, cols), "status": (T, cols), "applied": (T, cols), "x": (rows, self.nx, cols),
+                  "P": (rows, self.np_, cols)}
+        if out is None:
+            if keep.mem == MEM_DEVICE:
+                import torch
+                dev = keep.keep[0].device
+                out = {k: torch.empty(shapes[k], dtype=getattr(torch, np.dtype(dts[k]).name), device=dev) for k in names}
+            else:
+                out = {k: np.empty(shapes[k], dts[k]) for k in names}
+        tor = [_is_torch(v) for v in out.values()]
+        if any(tor) != all(tor):
+            raise ValueError("tick_many_trace: the outputs must live in the same memory")
+        to = _lib.TraceOut()
+        for k, v in out.items():
+            want = shapes[k]
+            if len(v.shape) != len(want) or v.shape[0] < want[0] or tuple(v.shape[1:]) != want[1:]:
+                raise ValueError(f"tick_many_trace: {k} has shape {tuple(v.shape)}, want {want} (or more rows)")
+            name = np.dtype(dts[k]).name
+            if tor[0]:
+                if not v.is_cuda or not v.is_contiguous() or str(v.dtype) != "torch." + name:
+                    raise TypeError(f"tick_many_trace: a torch {k} must be a contiguous {name} device tensor")
+            elif not isinstance(v, np.ndarray) or v.dtype != dts[k] or not v.flags.c_contiguous or not v.flags.writeable:
+                raise TypeError(f"tick_many_trace: a host {k} must be a writable C-contiguous {name} numpy array")
+            setattr(to, k, v.data_ptr() if tor[0] else v.ctypes.data)
+        to.mem = MEM_DEVICE if tor[0] else MEM_HOST
+        to.pitch = 0 if cols == self.n else cols
+        to.every = ev
+        check(load().fmskf_tick_many_trace(self.h, C.byref(ti), T, stride, C.byref(to)), "tick_many_trace")
+        return out
+
     # ------------------------------------------------------------------ readout
     def get_state(self):
         x = np.empty((self.nx, self.n), self.dtype)
