@@ -289,7 +289,7 @@ int fmskf_comm_init(fmskf_handle h, const uint8_t id[FMSKF_COMM_ID_BYTES], int r
 
 int fmskf_comm_info(fmskf_handle h, int *world, int *rank) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::comm_info);
     if (!h->comm) fail(FMSKF_EINVAL, "the handle has no communicator (fmskf_comm_init)");
     const RcclApi &a = need_rccl();
     int w = 0, r = -1;
@@ -387,10 +387,12 @@ void ens_async_begin(fmskf_ctx *h, const fmskf_tick_inputs *in) {
     const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
     h->time_begin();
     int e = 0;
-    if (h->cfg.model == FMSKF_MODEL_KF6) e = launch_kf6(h->s, t, h->kf6, libm, true, true, h->stream, &nb);
+    Kf6Zero z = zero_begin(h);
+    if (h->cfg.model == FMSKF_MODEL_KF6) e = launch_kf6(h->s, t, h->kf6, libm, true, true, h->stream, &nb, &z);
     else if (h->cfg.model == FMSKF_MODEL_EKF9) e = launch_ekf9(h->s, t, h->ekf9, libm, true, true, h->stream, &nb);
     else e = launch_kf12d(h->s, t, h->kf12, true, true, h->stream, &nb);
     launch_check(e, "tick kernel launch");
+    zero_launched(h, z);
     h->time_end();
     ens_carry_launched(h, C, t);
   } else {
@@ -428,7 +430,7 @@ int fmskf_ensemble_end(fmskf_handle h, double *mean, double *cov_packed) {
 int fmskf_ensemble_end_count(fmskf_handle h, double *mean, double *cov_packed, double *count,
                              uint32_t *n_records) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::ensemble_end);
     if (h->ens_pending == 0) fail(FMSKF_EINVAL, "no ensemble pending (fmskf_*ensemble_begin)");
     DeviceGuard g(h->cfg.device);
     fmskf_ctx::EnsSlot &S = h->eslot[h->ens_head];
@@ -457,7 +459,7 @@ int fmskf_ensemble_end_count(fmskf_handle h, double *mean, double *cov_packed, d
 
 int fmskf_ensemble_exchange_ms(fmskf_handle h, float *ms) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::ensemble_xms);
     if (!ms) fail(FMSKF_EINVAL, "null ms");
     *ms = h->ens_xms;
   });

@@ -401,7 +401,7 @@ int fmskf_set_timing(fmskf_handle h, int enable) {
 
 int fmskf_kernel_time_total(fmskf_handle h, double *total_ms, uint32_t *count) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::timing);
     if (!total_ms || !count) fail(FMSKF_EINVAL, "null argument");
     DeviceGuard g(h->cfg.device);
     double sum = 0.0;
@@ -418,7 +418,7 @@ int fmskf_kernel_time_total(fmskf_handle h, double *total_ms, uint32_t *count) {
 
 int fmskf_last_kernel_ms(fmskf_handle h, float *ms) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::timing);
     if (!ms) fail(FMSKF_EINVAL, "null ms");
     if (!h->timing) fail(FMSKF_EINVAL, "timing not enabled");
     DeviceGuard g(h->cfg.device);

@@ -183,6 +183,12 @@ struct fmskf_ctx {
   // (ISR, tick + ensemble record) take their fallbacks.
   bool gate_on = false;
   fmskf::GateDev gate{};
+  // KF6 zero flags (fmskf_internal.hpp Kf6Zero), allocated with the state.  zero_ok: the tuning
+  // makes zero cross planes possible (convert_params); zero_trust: nothing but flag-maintaining
+  // ticks has touched P since the flags were rebuilt; zero_prev: the trust before this API entry
+  // (check_handle below keeps both)
+  uint32_t *zero_flags = nullptr;
+  bool zero_ok = false, zero_trust = false, zero_prev = false;
   // per-row innovation gate (fmskf_set_row_gate; EKF9 without FMSKF_CFG_COMP_POS, diagonal R):
   // thresholds and the per-robot state planes, allocated when a row gate is first set.  While
   // rowgate_on, every EKF9 measurement update goes through ekf9_tick_launch's gated kernels and
@@ -389,8 +395,45 @@ struct fmskf_ctx {
 namespace fmskf {
 namespace capi {
 
-inline void check_handle(fmskf_handle h) {
+// Trust in the KF6 zero flags (fmskf_ctx::zero_trust) is a host decision, denied by default: a
+// tick may skip loads only if nothing but flag-maintaining ticks has touched P since the flags
+// were last rebuilt.  Every API entry passes check_handle, and check_handle drops the trust; the
+// flag-aware tick reads the trust that held before its own entry (zero_begin) and re-establishes
+// it behind its launch (zero_launched).  The entries below, which cannot write x or P, restore the
+// trust their entry dropped.  When in doubt a call is not listed: an untrusted tick costs one tick
+// of full loads, which rebuilds the flags, and nothing else.
+enum class Entry {
+  other,
+  sync,              // waits for the stream
+  get_config,        // copies the host's config struct
+  get_counters,      // reads the counters (and host-side tallies)
+  comm_info,         // asks the communicator for its size and rank
+  ensemble_end,      // fmskf_ensemble_end / _end_count: queues a fold of block records, waits, combines on the host
+  ensemble_xms,      // fmskf_ensemble_exchange_ms: a host float
+  timing,            // fmskf_last_kernel_ms / fmskf_kernel_time_total: event times
+  get_state,         // fmskf_get_state / _get_pose / _get_vel: copy x and P out
+};
+constexpr bool keeps_zero_trust(Entry e) { return e != Entry::other; }
+
+inline void check_handle(fmskf_handle h, Entry e = Entry::other) {
   if (!h) fail(FMSKF_EINVAL, "null handle");
+  h->zero_prev = h->zero_trust;
+  h->zero_trust = keeps_zero_trust(e) && h->zero_prev;
+}
+// the flags and the trust a KF6 full tick launches with; null flags = the kernels without them
+// (a handle whose tuning couples the blocks, and every captured launch: a replay must never carry
+// a baked-in trust bit)
+// The caller may also capture the handle's stream itself (window_call refuses such calls for the
+// same reason): the stream is asked, not only the handle.
+inline Kf6Zero zero_begin(const fmskf_ctx *h) {
+  bool captured = h->capturing;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (!captured && h->zero_ok && h->stream)
+    captured = hipStreamIsCapturing(h->stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+  return {h->zero_ok && !captured ? h->zero_flags : nullptr, h->zero_prev, false};
+}
+inline void zero_launched(fmskf_ctx *h, const Kf6Zero &z) {
+  if (z.used) h->zero_trust = true;
 }
 
 // Small host-resident inputs / outputs (<= 1 MiB per call) are zero-copy: the CPU packs the
@@ -452,9 +495,10 @@ void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, ui
               uint64_t stride);
 // the KF6 tick / correct / predict launch of a handle: the gated kernels while a gate is set and
 // the call updates, the plain ones otherwise
-inline int kf6_tick_launch(fmskf_ctx *h, const TickIn &t, bool libm, bool upd, bool pred) {
+// z: the zero flags of a direct tick (zero_begin), null for the launches that do not maintain them
+inline int kf6_tick_launch(fmskf_ctx *h, const TickIn &t, bool libm, bool upd, bool pred, Kf6Zero *z = nullptr) {
   if (h->gate_on && upd) return launch_kf6_gate(h->s, t, h->kf6, h->gate, libm, pred, h->stream);
-  return launch_kf6(h->s, t, h->kf6, libm, upd, pred, h->stream);
+  return launch_kf6(h->s, t, h->kf6, libm, upd, pred, h->stream, nullptr, z);
 }
 // zero the gate state planes (no-op while none are allocated)
 void zero_gate(fmskf_ctx *h);

@@ -90,6 +90,14 @@ void convert_params(fmskf_ctx *h) {
     for (int b = 0; b <= a; b++) h->kf12.r2[a * (a + 1) / 2 + b] = c.r[(a + 4) * (a + 5) / 2 + (b + 4)];
   h->kf12.decor = kf12d_cinv(h->kf12.r, h->kf12.cinv) ? 1 : 0;
   h->kf12.sparse = h->kf12.decor && kf12d_sparse(h->kf12.cinv, h->kf12.q) ? 1 : 0;
+  // KF6: the Q and R entries that couple (theta, omega) with (px, py, vx, vy) are exactly zero, so
+  // the cross-covariance planes can stay zero and the zero-load kernels are worth choosing (they
+  // are correct under any tuning: the flags are formed from the stored bits).  Packed Q 3 4 8 12 15
+  // 16 18 19 (the cross planes of P), packed R 3 4 6 7 (z = theta, omega, vx, vy)
+  bool ok = c.model == FMSKF_MODEL_KF6 && !(c.flags & FMSKF_CFG_COMP_POS);
+  for (int k : {3, 4, 8, 12, 15, 16, 18, 19}) ok = ok && h->kf6.q[k] == 0.f;
+  for (int k : {3, 4, 6, 7}) ok = ok && h->kf6.r[k] == 0.f;
+  h->zero_ok = ok;
 }
 
 }  // namespace
@@ -363,13 +371,15 @@ void run_tick(fmskf_ctx *h, const fmskf_tick_inputs *in, bool upd, bool pred, ui
   if (rs_pred) rs_prev_materialize(h);  // the predict reads the prev planes
   h->time_begin();
   int e = 0;
+  Kf6Zero z = zero_begin(h);
   switch (h->cfg.model) {
     case FMSKF_MODEL_RS: e = launch_rs(h->s, t, libm, upd, pred, h->stream); break;
-    case FMSKF_MODEL_KF6: e = kf6_tick_launch(h, t, libm, upd, pred); break;
+    case FMSKF_MODEL_KF6: e = kf6_tick_launch(h, t, libm, upd, pred, &z); break;
     case FMSKF_MODEL_EKF9: e = ekf9_tick_launch(h, t, libm, upd, pred); break;
     case FMSKF_MODEL_KF12D: e = launch_kf12d(h->s, t, h->kf12, upd, pred, h->stream); break;
   }
   launch_check(e, "tick kernel launch");
+  zero_launched(h, z);
   ens_carry_launched(h, C, t);
   // the predict stored the sums it read as the previous ones
   if (rs_pred) h->rs_prev_synced = t.msum_lo != nullptr;
@@ -538,6 +548,12 @@ int fmskf_create(const fmskf_config *cfg, fmskf_handle *out) {
       // KF6 / EKF9 with FMSKF_CFG_COMP_POS: the position low parts, tiled like x and P
       s.xlo = (cfg->flags & FMSKF_CFG_COMP_POS) ? h->alloc<float>((size_t)kKf6LoRows * s.pitch) : nullptr;
       h->kf6.lo = s.xlo;
+      // KF6: the zero flags, one word per 64-robot chunk (rebuilt by the first tick that uses them)
+      if (cfg->model == FMSKF_MODEL_KF6) {
+        const size_t words = (size_t)((n + 63) / 64);
+        h->zero_flags = h->alloc<uint32_t>(words);
+        hip_check(hipMemset(h->zero_flags, 0, words * 4), "zero flags");
+      }
       // the WT901 / motor ingest state (~470 B per robot) is allocated on first use
       // (ensure_imu / ensure_motors): a handle fed tick inputs by the caller holds only x, P
       s.counters = h->alloc<unsigned long long>(8);
@@ -685,7 +701,7 @@ int fmskf_graph_launch(fmskf_handle h, uint32_t times) {
 
 int fmskf_sync(fmskf_handle h) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::sync);
     DeviceGuard g(h->cfg.device);
     hip_check(hipStreamSynchronize(h->stream), "hipStreamSynchronize");
   });
@@ -693,7 +709,7 @@ int fmskf_sync(fmskf_handle h) {
 
 int fmskf_get_config(fmskf_handle h, fmskf_config *out) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::get_config);
     if (!out) fail(FMSKF_EINVAL, "null out");
     *out = h->cfg;
   });
@@ -764,7 +780,7 @@ int fmskf_tick_many(fmskf_handle h, const fmskf_tick_inputs *in, uint32_t n_tick
 
 int fmskf_get_pose(fmskf_handle h, float *x, float *y, float *th, uint32_t mem) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::get_state);
     DeviceGuard g(h->cfg.device);
     const uint64_t n = h->s.n;
     launch_check(launch_readout(h->s, h->readout, h->stream), "readout");
@@ -777,7 +793,7 @@ int fmskf_get_pose(fmskf_handle h, float *x, float *y, float *th, uint32_t mem) 
 
 int fmskf_get_vel(fmskf_handle h, float *vx, float *vy, float *vth, uint32_t mem) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::get_state);
     DeviceGuard g(h->cfg.device);
     const uint64_t n = h->s.n;
     launch_check(launch_readout(h->s, h->readout, h->stream), "readout");
@@ -790,7 +806,7 @@ int fmskf_get_vel(fmskf_handle h, float *vx, float *vy, float *vth, uint32_t mem
 
 int fmskf_get_state(fmskf_handle h, void *x, void *p_packed, uint32_t mem) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::get_state);
     DeviceGuard g(h->cfg.device);
     const uint64_t n = h->s.n;
     const Dims d = h->d;

@@ -158,7 +158,7 @@ int fmskf_set_state_lo(fmskf_handle h, const float *lo, uint32_t mem) {
 
 int fmskf_get_counters(fmskf_handle h, uint64_t *counters, uint32_t n_counters) {
   return guarded([&] {
-    check_handle(h);
+    check_handle(h, Entry::get_counters);
     if (!counters || n_counters == 0) return;
     DeviceGuard g(h->cfg.device);
     unsigned long long tmp[8];
@@ -230,9 +230,11 @@ int fmskf_tick_ensemble(fmskf_handle h, const fmskf_tick_inputs *in, double *out
       int nb = 0;
       const bool libm = h->cfg.trig == FMSKF_TRIG_LIBM;
       h->time_begin();
-      if (h->cfg.model == FMSKF_MODEL_KF6)
-        launch_check(launch_kf6(h->s, t, h->kf6, libm, true, true, h->stream, &nb), "tick kernel launch");
-      else if (h->cfg.model == FMSKF_MODEL_EKF9)
+      if (h->cfg.model == FMSKF_MODEL_KF6) {
+        Kf6Zero z = zero_begin(h);
+        launch_check(launch_kf6(h->s, t, h->kf6, libm, true, true, h->stream, &nb, &z), "tick kernel launch");
+        zero_launched(h, z);
+      } else if (h->cfg.model == FMSKF_MODEL_EKF9)
         launch_check(launch_ekf9(h->s, t, h->ekf9, libm, true, true, h->stream, &nb), "tick kernel launch");
       else
         launch_check(launch_kf12d(h->s, t, h->kf12, true, true, h->stream, &nb), "tick kernel launch");

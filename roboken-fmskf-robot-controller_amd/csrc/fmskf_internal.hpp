@@ -472,9 +472,19 @@ struct Wt901Cfg {
 // launchers (return hipError_t as int)
 int launch_rs(const DevState &s, const TickIn &in, bool libm, bool correct, bool predict,
               hipStream_t st);
+// The zero flags of a KF6 handle (kf6_lane.hpp kKf6ZeroLoad): one word per 64-robot chunk,
+// ceil(N / 64) words, set = the chunk's robots all hold the bit pattern 0 in the load-mask planes.
+// Derived data: allocated with the state, in no checkpoint, not part of the ABI.  A caller that
+// keeps track of who wrote P (api_ctx.hpp zero_trust) passes them to launch_kf6 with whether this
+// launch may trust them; `used` comes back true when a flag-maintaining kernel (Opt ZL) was launched.
+struct Kf6Zero {
+  uint32_t *flags;
+  bool trusted;
+  bool used;
+};
 // in.ens_blocks set (upd and pred only): *ens_nb receives the grid, i.e. the record count
 int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, bool upd,
-               bool pred, hipStream_t st, int *ens_nb = nullptr);
+               bool pred, hipStream_t st, int *ens_nb = nullptr, Kf6Zero *z = nullptr);
 // the gated KF6 measurement update (kernels_kf6.hip), with the predict (pred) or alone; plain
 // state only (no FMSKF_CFG_COMP_POS), no fused ensemble record
 int launch_kf6_gate(const DevState &s, const TickIn &in, const Kf6Params &p, const GateDev &g, bool libm,

@@ -11,6 +11,15 @@
 // other launch their position half (kKf6SkipMask); the kernels without WIDE are the code they
 // were before the split (profiles/kf6_half_cache_bodies.json).
 //
+// In that same half-cache regime a direct launch also leaves out the loads of the cross planes its
+// wave is known to hold zero (Opt ZL on ZeroArgs; kf6_lane.hpp kKf6ZeroLoad, kf6_zero_loads in
+// launch_regime.hpp): one flag word per 64-robot chunk, read through the scalar path ahead of the
+// state loads, a wave-uniform branch around the masked planes' loads (issued last), the new word
+// stored by lane 0 of the owning wave behind the state.  Memory holds every plane of every robot
+// as an unconditional tick leaves it; whether a launch may trust the flags is the host's decision
+// (api_ctx.hpp check_handle), never a captured one.  The kernels without ZL are the code they
+// were (profiles/kf6_zero_loads_bodies.json).
+//
 // A plain full tick launched right behind an asynchronous ensemble event carries that event's
 // fold (Opt FOLD): the LEN fold blocks of ens_fold_front ahead of its tick blocks, as the record
 // tick of the next event would carry them, and no record epilogue.  The host decides (run_tick);
@@ -142,6 +151,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
   Kf6In m[R];
   float xs[O::ENS ? R : 1][6];
   bool lv[R];
+  uint32_t zf[O::ZL ? R : 1];  // ZL: the robots' chunk words, read up front with the inputs
+  if constexpr (O::ZL) {
+#pragma unroll
+    for (int r = 0; r < R; r++) zf[r] = kf6_zero_flag(aa.flags, min(i0 + r * G, last));
+  }
   if (O::UPD) {
 #pragma unroll
     for (int r = 0; r < R; r++) m[r] = kf6_load_in<O>(a.in, n, 0, min(i0 + r * G, last));
@@ -152,7 +166,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
     const bool live = i < nn;
     Kf6Lo<O> lo;
     Kf6GateOf<O, A> gt;
-    kf6_load_state<O>(a.x, a.P, a.pitch, live ? i : last, x, P);
+    if constexpr (O::ZL) kf6_load_state_zl<O>(a.x, a.P, live ? i : last, aa.trusted && zf[r], x, P);
+    else kf6_load_state<O>(a.x, a.P, a.pitch, live ? i : last, x, P);
     const auto old = kf6_keep_old<kf6_mask<O>()>(P);
     kf6_load_lo<O>(a.prm.lo, live ? i : last, lo);
     gt.load(gate_dev(aa), live ? i : last, n);
@@ -162,6 +177,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
       kf6_store_state<O>(a.x, a.P, a.pitch, i, x, P, old);
       kf6_store_lo<O>(a.prm.lo, i, lo);
       gt.store(gate_dev(aa), i, n);
+    }
+    if constexpr (O::ZL) {
+      // the chunk's word after this tick, stored by lane 0 of the wave that owns the chunk (lane 0
+      // live; a wave wholly past N has seen one robot of another wave's chunk and stores nothing):
+      // where it changed, or in an untrusted launch always (the rebuild)
+      const uint32_t nf = kf6_zero_now(P) ? 1u : 0u;
+      if (live && (threadIdx.x & 63u) == 0 && (!aa.trusted || nf != zf[r])) aa.flags[i / kZeroChunk] = nf;
     }
     nan_guard(x, P, a.counters, live);
     if constexpr (O::ENS) {
@@ -176,9 +198,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(WPE, 8))
 // A FOLD instantiation on the tick grid g: the LEN fold blocks of the pending ensemble event
 // ahead of the tick blocks, as launch_ens_o launches a record tick that carries one
 template <class A>
-static void launch_fold(void (*k)(A), A a, unsigned g, unsigned lds, hipStream_t st) {
-  a.in.ens_grid = g;
-  launch_signal(k, dim3(g + (unsigned)EnsRec<6>::LEN), lds, st, a.in.ens_done, a);
+static void launch_fold(void (*k)(A), A aa, unsigned g, unsigned lds, hipStream_t st) {
+  kf_args_mut(aa).in.ens_grid = g;
+  launch_signal(k, dim3(g + (unsigned)EnsRec<6>::LEN), lds, st, kf_args(aa).in.ens_done, aa);
 }
 
 // One robot per lane: k_kf6t, or for a gated handle k_kf6p's single-robot form, the shape its
@@ -193,8 +215,9 @@ static void launch_one(const A &aa, unsigned lds, hipStream_t st) {
 }
 
 // A: Kf6Args, or GateArgs for a gated handle (bytes per robot: + the gate word and the NIS)
+// z: the handle's zero flags where the caller maintains their trust (Kf6Zero), else null
 template <class O, class A>
-static void launch_o(const A &aa, hipStream_t st) {
+static void launch_o(const A &aa, hipStream_t st, Kf6Zero *z = nullptr) {
   constexpr bool GATED = std::is_same<A, GateArgs>::value;
   const Kf6Args &a = kf_args(aa);
   if constexpr (GATED && !O::PRED) {  // the gated fmskf_correct: one robot per lane, uncapped
@@ -214,13 +237,23 @@ static void launch_o(const A &aa, hipStream_t st) {
         // the ungated full tick: streamed, with the wide mask (kf6_wide; never COMP, whose
         // kernels stay as they were) and / or carrying a pending ensemble fold (run_tick)
         const bool wide = !O::COMP && kf6_wide(a.n), fold = a.in.fold_blocks != nullptr;
+        // the wide mask's kernels with the loads of known zeros left out (Opt ZL)
+        // (zl implies wide: the lambda below has no kernel for Z without W, nor for COMP)
+        const bool zl = wide && z && z->flags && kf6_zero_loads(a.n);
         if (r.nt || wide || fold) {
-          with_bools([&](auto N, auto W, auto F) {
+          with_bools([&](auto N, auto W, auto F, auto Z) {
             using ON = std::conditional_t<N(), WithNT<O>, O>;
             using OW = std::conditional_t<W() && !O::COMP, WithWide<ON>, ON>;
-            if constexpr (F()) launch_fold(k_kf6p<4, 2, WithFold<OW>, A>, aa, g, r.lds, st);
-            else k_kf6p<4, 2, OW, A><<<g, kBlock, r.lds, st>>>(aa);
-          }, r.nt, wide, fold);
+            if constexpr (Z() && W() && !O::COMP) {
+              const ZeroArgs za{aa, z->flags, z->trusted ? 1u : 0u};
+              if constexpr (F()) launch_fold(k_kf6p<4, 2, WithZero<WithFold<OW>>, ZeroArgs>, za, g, r.lds, st);
+              else k_kf6p<4, 2, WithZero<OW>, ZeroArgs><<<g, kBlock, r.lds, st>>>(za);
+              z->used = true;
+            } else if constexpr (!Z()) {
+              if constexpr (F()) launch_fold(k_kf6p<4, 2, WithFold<OW>, A>, aa, g, r.lds, st);
+              else k_kf6p<4, 2, OW, A><<<g, kBlock, r.lds, st>>>(aa);
+            }
+          }, r.nt, wide, fold, zl);
           return;
         }
       }
@@ -243,38 +276,47 @@ static void launch_o(const A &aa, hipStream_t st) {
 // per lane (half the block reductions per robot) measured slower: K = 1 at 2^20 40.8-41.0 us
 // per tick against 38.6-39.0 (kbench, two alternating passes)
 template <class O>
-static int launch_ens_o(KfArgs<MdKF6, Kf6Params> a, hipStream_t st) {
+static int launch_ens_o(KfArgs<MdKF6, Kf6Params> a, hipStream_t st, Kf6Zero *z) {
   using E = WithEns<O>;
   const unsigned carry = a.in.fold_blocks ? (unsigned)EnsRec<6>::LEN : 0u;
   const LaunchRegime r = kf6_ens_regime(a.n, O::COMP);
   const unsigned g = r.two ? (unsigned)((a.n + 2 * kBlock - 1) / (2 * kBlock)) : grid_for(a.n).x;
   a.in.ens_grid = g;
   // two per lane: the write-back mask of the plain tick of the same regime (kf6_wide)
-  with_bools([&](auto TWO, auto N, auto W) {
+  const bool wide = r.two && !O::COMP && kf6_wide(a.n);
+  // the last bool implies wide, and wide implies two: the combinations without a kernel below
+  with_bools([&](auto TWO, auto N, auto W, auto Z) {
     using EN = std::conditional_t<N(), WithNT<E>, E>;
     if constexpr (TWO()) {
       using EW = std::conditional_t<W() && !O::COMP, WithWide<EN>, EN>;
-      launch_signal(k_kf6p<4, 2, EW>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
-    } else if constexpr (!W()) {
+      if constexpr (Z() && W() && !O::COMP) {
+        const ZeroArgs za{a, z->flags, z->trusted ? 1u : 0u};
+        launch_signal(k_kf6p<4, 2, WithZero<EW>, ZeroArgs>, dim3(g + carry), r.lds, st, a.in.ens_done, za);
+        z->used = true;
+      } else if constexpr (!Z()) {
+        launch_signal(k_kf6p<4, 2, EW>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
+      }
+    } else if constexpr (!W() && !Z()) {
       launch_signal(k_kf6t<4, EN>, dim3(g + carry), r.lds, st, a.in.ens_done, a);
     }
-  }, r.two, r.nt, r.two && !O::COMP && kf6_wide(a.n));
+  }, r.two, r.nt, wide, wide && z && z->flags && kf6_zero_loads(a.n));
   return (int)g;
 }
 
 template <class O>
-static void launch_sel(const KfArgs<MdKF6, Kf6Params> &a, hipStream_t st, int *ens_nb) {
+static void launch_sel(const KfArgs<MdKF6, Kf6Params> &a, hipStream_t st, int *ens_nb, Kf6Zero *z) {
   if constexpr (O::UPD && O::PRED) {
     if (ens_nb) {
-      *ens_nb = launch_ens_o<O>(a, st);
+      *ens_nb = launch_ens_o<O>(a, st, z);
       return;
     }
   }
-  launch_o<O>(a, st);
+  launch_o<O>(a, st, z);
 }
 
 int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool libm, bool upd,
-               bool pred, hipStream_t st, int *ens_nb) {
+               bool pred, hipStream_t st, int *ens_nb, Kf6Zero *z) {
+  if (z) z->used = false;
   KfArgs<MdKF6, Kf6Params> a{s.n, s.pitch, (float *)s.x, (float *)s.P, in, s.counters, p};
   const bool small = kf6_small(s);  // Opt::SMALL
   const bool valid = upd && in.valid != nullptr, rec = upd && in.rec != nullptr;
@@ -286,7 +328,7 @@ int launch_kf6(const DevState &s, const TickIn &in, const Kf6Params &p, bool lib
     return (int)hipErrorInvalidValue;
   if (upd) {
     with_bools([&](auto LIBM, auto PRED, auto REC, auto COMP, auto SMALL, auto VALID) {
-      launch_sel<Opt<LIBM(), true, PRED(), SMALL(), VALID(), REC(), false, false, COMP()>>(a, st, nb);
+      launch_sel<Opt<LIBM(), true, PRED(), SMALL(), VALID(), REC(), false, false, COMP()>>(a, st, nb, z);
     }, libm, pred, rec, comp, small, valid);
   } else {  // a predict reads no input: SMALL, VALID and REC cannot change its code
     with_bools([&](auto LIBM, auto COMP) {

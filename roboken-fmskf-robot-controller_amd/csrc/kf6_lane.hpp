@@ -24,7 +24,7 @@ struct Opt {
   static constexpr bool LIBM = LIBM_, UPD = UPD_, PRED = PRED_, SMALL = SMALL_, VALID = VALID_,
                         REC = REC_, NT = NT_, ENS = ENS_, COMP = COMP_;
   static constexpr int CP = NT_ ? kStateNT : 0;
-  static constexpr bool WIDE = false, FOLD = false;
+  static constexpr bool WIDE = false, FOLD = false, ZL = false;
   using Plain = Opt;
 };
 template <class O>
@@ -48,6 +48,16 @@ template <class O>
 using WithWide = OptX<typename O::Plain, true, O::FOLD>;
 template <class O>
 using WithFold = OptX<typename O::Plain, O::WIDE, true>;
+// ZL: the launch skips the loads of the cross planes its wave is known to hold zero (kKf6ZeroLoad
+// below, ZeroArgs); on WIDE instantiations only, applied after WithWide / WithFold.  A type of its
+// own for the same reason: the kernels without it keep their symbols and their code.
+template <class O>
+struct OptZ : O {
+  static_assert(O::WIDE && !O::COMP, "zero-load skipping rides on the wide write-back mask");
+  static constexpr bool ZL = true;
+};
+template <class O>
+using WithZero = OptZ<O>;
 
 // the compensated entries of COMP: x 0-1 (px, py), packed P 0-2 (P00, P10, P11)
 constexpr unsigned kKf6CXM = kPosCXM;
@@ -73,10 +83,23 @@ struct GateArgs {
   Kf6Args k;
   GateDev g;
 };
+// The ZL instantiations take the plain arguments wrapped the same way: then the handle's zero
+// flags (one word per 64-robot chunk, below) and whether this launch may trust them.
+struct ZeroArgs {
+  Kf6Args k;
+  uint32_t *flags;
+  uint32_t trusted;
+};
 struct NoGate {};
 __host__ __device__ __forceinline__ const Kf6Args &kf_args(const Kf6Args &a) { return a; }
 __host__ __device__ __forceinline__ const Kf6Args &kf_args(const GateArgs &a) { return a.k; }
+__host__ __device__ __forceinline__ const Kf6Args &kf_args(const ZeroArgs &a) { return a.k; }
+// the launchers' own copy, which they complete (ens_grid): a name of its own, so that no call of
+// kf_args resolves differently
+inline Kf6Args &kf_args_mut(Kf6Args &a) { return a; }
+inline Kf6Args &kf_args_mut(ZeroArgs &a) { return a.k; }
 __device__ __forceinline__ NoGate gate_dev(const Kf6Args &) { return {}; }
+__device__ __forceinline__ NoGate gate_dev(const ZeroArgs &) { return {}; }
 __device__ __forceinline__ const GateDev &gate_dev(const GateArgs &a) { return a.g; }
 
 template <int CP = 0>
@@ -219,6 +242,70 @@ __device__ __forceinline__ void kf6_store_state(float *xg, float *Pg, uint64_t, 
   for (int k = 0; k < 6; k++) st_f32<SP>(rx, c, k * W * 4, x[k]);
 #pragma unroll
   for (int k = 0; k < 21; k++) kf6_st_p<SP>(rp, c, k * W * 4, k, P[k], old);
+}
+
+// Loads of zeros left out (Opt ZL).  Under a block-diagonal tuning the cross planes are +0.0 in
+// every robot at every tick, and the wide write-back mask already stores none of them; the planes
+// in kKf6ZeroLoad (a subset of kKf6SkipWide) are then not loaded either.  The handle owns one word
+// per 64-robot chunk (Kf6Zero, fmskf_internal.hpp): set = those planes hold the bit pattern 0 in
+// memory for every robot of the chunk (-0.0 is not zero here).  A wave's 64 robots, the clamped
+// ones included, lie in one chunk, so the word and the branch on it are wave-uniform: a branch
+// around the loads, not a select of a loaded value.  The always-needed rows are issued first; a
+// skipped plane is +0.0f with 0 as its remembered bits, so compute and write-back are the same
+// operations on the same values as after loading the zeros, and memory ends up holding what an
+// unconditional tick leaves.  The flags are only as good as the host's knowledge of who wrote P
+// since they were rebuilt: the launch says whether it trusts them (ZeroArgs::trusted; the rule is
+// in api_ctx.hpp), and an untrusted one loads everything and rewrites every word.
+// The mask is all eight cross planes: the largest one with which every KF6-fed row of a --full
+// bench line still reads frac <= 0.97 against the 232 B price (headline 0.957; the position half
+// alone read 0.924 and gained 1.9 %, less than five times the parent's spread, against 5.4 %;
+// profiles/kf6_zero_loads_ab.json).  -DFMSKF_KF6_ZERO_LOAD_MASK builds another subset.
+#ifndef FMSKF_KF6_ZERO_LOAD_MASK
+#define FMSKF_KF6_ZERO_LOAD_MASK kKf6SkipWide
+#endif
+constexpr uint32_t kKf6ZeroLoad = FMSKF_KF6_ZERO_LOAD_MASK;
+static_assert(kKf6ZeroLoad != 0 && (kKf6ZeroLoad & ~kKf6SkipWide) == 0, "cross planes of the wide mask only");
+constexpr uint32_t kZeroChunk = 64;  // robots per flag word: one wave's
+// the chunk word of (clamped) robot ic, read through the scalar path: no vmcnt slot
+__device__ __forceinline__ uint32_t kf6_zero_flag(const uint32_t *flags, uint32_t ic) {
+  return flags[(uint32_t)__builtin_amdgcn_readfirstlane(ic) / kZeroChunk];
+}
+// kf6_load_state with the kKf6ZeroLoad planes last and, with `skip` (wave-uniform), not at all
+template <class O>
+__device__ __forceinline__ void kf6_load_state_zl(const float *xg, const float *Pg, uint32_t i, bool skip,
+                                                  float (&x)[6], float (&P)[21]) {
+  constexpr uint32_t W = tile_w<float>();
+  const uint32_t tl = (uint32_t)__builtin_amdgcn_readfirstlane(i / W);
+  const uint32_t c = (i - tl * W) * 4u;
+  const auto rx = rsrc(xg + (uint64_t)tl * (6 * W), 6 * W * 4), rp = rsrc(Pg + (uint64_t)tl * (21 * W), 21 * W * 4);
+#pragma unroll
+  for (int k = 0; k < 6; k++) x[k] = ld_f32<O::CP>(rx, c, k * W * 4);
+#pragma unroll
+  for (int k = 0; k < 21; k++)
+    if (!kf6_skip<kKf6ZeroLoad>(k)) P[k] = ld_f32<O::CP>(rp, c, k * W * 4);
+  // The zeros are written ahead of the branch, each into a register of its own that the
+  // conditional load then overwrites: a zero moved in on the skipping side of the branch would be
+  // a write to a register the other side has a load pending on, and the wait the compiler puts in
+  // front of it drains every load of the robot (measured in the listing: vmcnt(3) .. vmcnt(0)
+  // ahead of the first arithmetic).  Only the listing shows this: look at it again when the
+  // compiler changes.  From an asm statement, so that the value is a register like a loaded one
+  // and the arithmetic on it is not specialised.
+#pragma unroll
+  for (int k = 0; k < 21; k++)
+    if (kf6_skip<kKf6ZeroLoad>(k)) asm volatile("v_mov_b32 %0, 0" : "=v"(P[k]));
+  if (!skip) {
+#pragma unroll
+    for (int k = 0; k < 21; k++)
+      if (kf6_skip<kKf6ZeroLoad>(k)) P[k] = ld_f32<O::CP>(rp, c, k * W * 4);
+  }
+}
+// whether every lane of the wave holds the bit pattern 0 in every kKf6ZeroLoad plane
+__device__ __forceinline__ bool kf6_zero_now(const float (&P)[21]) {
+  uint32_t any = 0;
+#pragma unroll
+  for (int k = 0; k < 21; k++)
+    if (kf6_skip<kKf6ZeroLoad>(k)) any |= __builtin_bit_cast(uint32_t, P[k]);
+  return __builtin_amdgcn_ballot_w64(any != 0) == 0;
 }
 
 // the COMP low-part rows, tiled like x ([N/W][5][W], one scalar descriptor per tile)

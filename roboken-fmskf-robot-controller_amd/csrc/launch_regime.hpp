@@ -153,6 +153,21 @@ inline bool kf6_wide(uint64_t n) {
   return fits_half_cache(n * (kf6_state_bytes(false) + kKf6InBytes));
 }
 
+// Whether a two-per-lane full tick (ungated, not COMP) with the wide mask also leaves out the loads
+// of the cross planes its wave is known to hold zero (Opt ZL, kf6_lane.hpp kKf6ZeroLoad): the
+// half-cache regime of kf6_wide, for the same reason -- the headline row has room under the 232 B
+// price for the bytes no longer fetched (frac 0.901 -> 0.957), the rows past half the cache have
+// less (the 2^21 shard row reads 0.93 as it is; profiles/kf6_zero_loads_ab.json).  The launcher asks only where the wide
+// mask is taken, a direct launch has the handle's flags and the tuning can keep the planes zero.
+// FMSKF_KF6_ZERO_LOADS (read once): 0 off, 1 on wherever the wide mask is taken, unset by the regime.
+// The flag kernels exist with the wide mask only, and the knob does not move kf6_wide: past half
+// the cache 1 alone changes nothing, with FMSKF_KF6_SKIP_WIDE=1 it reaches every two-per-lane full tick.
+inline bool kf6_zero_loads(uint64_t n) {
+  const int force = FMSKF_ENV_INT("FMSKF_KF6_ZERO_LOADS", -1);
+  if (force == 0 || force == 1) return force == 1;
+  return fits_half_cache(n * (kf6_state_bytes(false) + kKf6InBytes));
+}
+
 // The fused KF6 tick + ensemble record: two per lane while state + one tick's inputs fit the
 // cache, nt on the state alone.  FMSKF_KF6_VARIANT is not consulted here
 inline LaunchRegime kf6_ens_regime(uint64_t n, bool comp) {

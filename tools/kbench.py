@@ -65,9 +65,14 @@ def main():
     ap.add_argument("--dense-qr", action="store_true",
                     help="KF6: Q and R with every off-diagonal at correlation 0.3 (the heading and the translation "
                          "blocks coupled, so every covariance plane changes on every tick)")
+    ap.add_argument("--zero-loads", type=int, choices=[0, 1], default=None,
+                    help="KF6: FMSKF_KF6_ZERO_LOADS for this run (0: the two-per-lane full tick loads every plane, "
+                         "1: it skips the loads of cross planes known to hold zero); unset: by the launch regime")
     ap.add_argument("--comm", action="store_true",
                     help="--op ens_async: a world-1 RCCL communicator on the handle (fmskf_comm_init)")
     args = ap.parse_args()
+    if args.zero_loads is not None:  # the library reads the knob once, at its first launch
+        os.environ["FMSKF_KF6_ZERO_LOADS"] = str(args.zero_loads)
     import numpy as np
     import torch
     import fmskf
@@ -315,7 +320,7 @@ def main():
     x, P = e.get_state()
     ok = bool(np.isfinite(x).all() and (P is None or np.isfinite(P).all()))
     print(json.dumps({"model": args.model, "n": n, "variant": os.environ.get("FMSKF_KF6_VARIANT", "0"),
-                      "valid_mask": args.valid,
+                      "valid_mask": args.valid, "zero_loads": os.environ.get("FMSKF_KF6_ZERO_LOADS", "regime"),
                       "op": args.op, "trig": args.trig, "many": args.many, "ms_per_tick": ms_tick,
                       "steps_per_s": n / (ms_tick * 1e-3),
                       "algo_GBps": BYTES[args.model] * n / (ms_tick * 1e-3) / 1e9, "finite": ok, **extra}),

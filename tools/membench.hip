@@ -838,8 +838,10 @@ __global__ void k_fill_rand(uint32_t *p, uint64_t words, uint32_t seed) {
 // in SKIP (bit k = row k, x rows 0-5, packed P plane p at row 6 + p) are stored only by the lanes
 // whose value changed (a bit compare that depends on the loads and the record), the others by
 // every lane.  chg = 0: nothing changes, so no SKIP row is stored by any wave; chg = 1: every
-// value changes, so the compares are paid and every store is issued
-template <int T, int LAUX, int SAUX, uint32_t SKIP>
+// value changes, so the compares are paid and every store is issued.  The rows in NOLD (a subset
+// of SKIP) are not loaded either: they stand for planes known to hold zero, so 0 is both their
+// value and their remembered old bits -- the ceiling of a tick that skips those loads
+template <int T, int LAUX, int SAUX, uint32_t SKIP, uint32_t NOLD = 0u>
 __global__ __launch_bounds__(256) void k_tiled_skip(uint32_t *st, const uint4 *raw, uint64_t n, uint32_t chg) {
   const uint64_t v = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (v >= n) return;
@@ -849,7 +851,8 @@ __global__ __launch_bounds__(256) void k_tiled_skip(uint32_t *st, const uint4 *r
   const uint32_t vo = threadIdx.x * 4u;
   uint32_t s[27];
 #pragma unroll
-  for (int k = 0; k < 27; k++) s[k] = __builtin_amdgcn_raw_buffer_load_b32(r, vo, k * T * 4, LAUX);
+  for (int k = 0; k < 27; k++)
+    s[k] = ((NOLD >> k) & 1u) ? 0u : __builtin_amdgcn_raw_buffer_load_b32(r, vo, k * T * 4, LAUX);
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const u32x4 q = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(raw) + v);
   const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
@@ -1353,7 +1356,9 @@ int main(int argc, char **argv) {
     // membench LG 1 skip: the tiled KF6 pattern with the write-back of k P planes left out where
     // unchanged (k_tiled_skip), k = 0, 4, 8, 13: does time follow the written bytes?  Plain loads
     // and sc1 stores while the state fits the Infinity Cache (LG <= 20), non-temporal past it, as
-    // the tick kernels choose.  Records from a ring of ticks; three interleaved passes.
+    // the tick kernels choose.  Records from a ring of ticks; three interleaved passes.  The
+    // skip8_noload4 / skip8_noload8 rows also leave out the loads of 4 / all 8 of the masked planes
+    // (planes known to hold zero): what a dropped load is worth next to skip8.
     hipEvent_t f0, f1;
     CK(hipEventCreate(&f0));
     CK(hipEventCreate(&f1));
@@ -1369,7 +1374,7 @@ int main(int argc, char **argv) {
     CK(hipDeviceSynchronize());
     const unsigned g = (unsigned)((n + 255) / 256);
     int tick = 0;
-    auto tm = [&](const char *name, int planes, uint32_t chg, auto launch) {
+    auto tm = [&](const char *name, int planes, int noload, uint32_t chg, auto launch) {
       for (int w = 0; w < 5; w++) launch(ib + (size_t)(tick++ % ring) * n, chg);
       CK(hipEventRecord(f0));
       for (int it = 0; it < 100; it++) launch(ib + (size_t)(tick++ % ring) * n, chg);
@@ -1378,29 +1383,34 @@ int main(int argc, char **argv) {
       float ms = 0;
       CK(hipEventElapsedTime(&ms, f0, f1));
       const double us = ms * 1e3 / 100;
-      printf("{\"n\": %llu, \"kernel\": \"%s\", \"nt\": %d, \"masked_planes\": %d, \"all_change\": %u, \"us\": %.2f, "
-             "\"bytes_moved\": %d}\n",
-             (unsigned long long)n, name, (int)nt, planes, chg, us, 232 - (chg ? 0 : 4 * planes));
+      printf("{\"n\": %llu, \"kernel\": \"%s\", \"nt\": %d, \"masked_planes\": %d, \"unloaded_planes\": %d, "
+             "\"all_change\": %u, \"us\": %.2f, \"bytes_moved\": %d}\n",
+             (unsigned long long)n, name, (int)nt, planes, noload, chg, us,
+             232 - (chg ? 0 : 4 * planes) - 4 * noload);
     };
     // packed P plane p is row 6 + p: B = {3, 4, 15, 16}, A = B + {8, 12, 18, 19}, 13 = A + {0, 2, 6, 9, 14}
     constexpr uint32_t MB = (1u << 9) | (1u << 10) | (1u << 21) | (1u << 22);
     constexpr uint32_t MA = MB | (1u << 14) | (1u << 18) | (1u << 24) | (1u << 25);
     constexpr uint32_t M13 = MA | (1u << 6) | (1u << 8) | (1u << 12) | (1u << 15) | (1u << 20);
-#define SKIPRUN(MASK, K, CHG, NAME)                                                                      \
-  tm(NAME, K, CHG, [&](const uint4 *in, uint32_t c) {                                                    \
-    if (nt) k_tiled_skip<2048, 2, 2, MASK><<<g, 256>>>(sb, in, n, c);                                    \
-    else k_tiled_skip<2048, 0, 16, MASK><<<g, 256>>>(sb, in, n, c);                                      \
+#define SKIPRUN_NL(MASK, NOLD, K, KNL, CHG, NAME)                                                        \
+  tm(NAME, K, KNL, CHG, [&](const uint4 *in, uint32_t c) {                                               \
+    if (nt) k_tiled_skip<2048, 2, 2, MASK, NOLD><<<g, 256>>>(sb, in, n, c);                              \
+    else k_tiled_skip<2048, 0, 16, MASK, NOLD><<<g, 256>>>(sb, in, n, c);                                \
   })
+#define SKIPRUN(MASK, K, CHG, NAME) SKIPRUN_NL(MASK, 0u, K, 0, CHG, NAME)
     for (int rep = 0; rep < 3; rep++) {
       SKIPRUN(0u, 0, 0u, "skip0");
       SKIPRUN(MB, 4, 0u, "skip4");
       SKIPRUN(MA, 8, 0u, "skip8");
+      SKIPRUN_NL(MA, MB, 8, 4, 0u, "skip8_noload4");
+      SKIPRUN_NL(MA, MA, 8, 8, 0u, "skip8_noload8");
       SKIPRUN(M13, 13, 0u, "skip13");
       SKIPRUN(0u, 0, 1u, "skip0_all_change");  // the control of the two below: no compares
       SKIPRUN(MB, 4, 1u, "skip4_all_change");
       SKIPRUN(MA, 8, 1u, "skip8_all_change");
     }
 #undef SKIPRUN
+#undef SKIPRUN_NL
     return 0;
   }
   if (argc > 3 && argv[3][0] == 'p') {
